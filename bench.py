@@ -11,11 +11,29 @@ warmup steps, an untimed rehearsal runs the timed launches on scratch counter
 rows and resets the engine to step 0, repeated for >= --rehearse-ms (50 ms),
 so a short timed region does not run on the GPU's idle clocks; the warmup and
 the timed K steps then run from the same state as without it.  Nothing inside
-the clock is instrumented: kernel and all-reduce times come from a replay of
-the same launches after it (--kernel-timing replay).
+the clock is instrumented.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what `value` needs: it sets the engine up, rehearses,
+warms up, times the K steps, writes the outputs (--dump-outputs) and prints
+the line.  --full adds every leg beside the timed region, each a run of its
+own after the clock: the kernel and all-reduce times (a replay of the same
+launches, --kernel-timing replay) with the rooflines they feed, the general
+kernel, the streaming leg, the Log Matching check, the handler batches, the
+CPU baseline and, at N > 1, the other scaling's leg.
+
+--dump-outputs DIR writes what the timed region computed, for comparing two
+builds output for output (the inputs are seeded: identical from run to run):
+DIR/counters.npy, the K timed steps' counter rows as a caller of
+raft_engine_step_async receives them (all ranks' sum; the last row is the
+last step's; of a very long run the last DUMP_COUNTER_BYTES worth);
+DIR/state_sample.npy, the state words after the last timed step of a fixed,
+seeded sample of this rank's groups (every group up to DUMP_SAMPLE_GROUPS);
+DIR/digest.npy, the engine's digest of every group's state and logs at that
+point as two 32-bit halves.  All float64 (exact for these integers).  Ranks
+above 0 write state_sample_rank<r>.npy / digest_rank<r>.npy.
 
 Multi-GPU: one process per GPU.  With --gpus N > 1 and no torch.distributed
 environment, this script spawns the N rank processes itself (fresh
@@ -24,8 +42,8 @@ status.  Groups never talk across GPUs, so the path shards with no data-path
 exchange.  By default `value` is BASELINE.json configs[3] ("config 4"): the
 same 10^6 groups split into contiguous global-id ranges over the N GPUs
 (strong scaling, `value` = 10^6 x steps / the MAX of the ranks' times).  The
-line then also carries `weak_scaling`, measured in the same job: every GPU its
-own 10^6 groups, timed the same way, whose rank-0 counter rows must equal the
+line of a --full run also carries `weak_scaling`, measured in the same job:
+every GPU its own 10^6 groups, timed the same way, whose rank-0 rows equal the
 strong leg's all-reduced rows (the same global groups).  --scaling weak swaps
 the two (the strong leg is then `config4_strong`).  The only collective is the
 all-reduce of the per-step counter rows over RCCL: one all-reduce of all the
@@ -68,6 +86,13 @@ PMC_FILE = os.path.join(ROOT, "profiles", "pmc_rows.json")
 # group-steps/s the rehearsal count assumes (above every measured rate: its
 # repeats last at least --rehearse-ms)
 REHEARSE_RATE = 3.0e10
+# --dump-outputs: the state sample is DUMP_SAMPLE_RUNS seeded runs of
+# DUMP_SAMPLE_RUN consecutive groups (32,768 groups: 27 MB as float64 at
+# R = 5, 55 MB at R = 8, the widest group) and the counter rows are the last
+# DUMP_COUNTER_BYTES worth of the timed steps, so a dump stays under 64 MB
+DUMP_SAMPLE_RUNS, DUMP_SAMPLE_RUN, DUMP_SEED = 32, 1024, 20240613
+DUMP_SAMPLE_GROUPS = DUMP_SAMPLE_RUNS * DUMP_SAMPLE_RUN
+DUMP_COUNTER_BYTES = 8_000_000
 SCHEDULES = {"auto": abi.SCHED_AUTO, "one": abi.SCHED_ONE_PER_WAVE, "balanced": abi.SCHED_BALANCED}
 
 
@@ -283,6 +308,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10_000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the timed region (after the clock): the kernel-time replay and "
+                         "its rooflines, the general kernel, the streaming leg, the Log Matching check, the handler "
+                         "batches, the CPU baseline and (N > 1) the other scaling's leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the timed region's outputs as DIR/<name>.npy (float64): the timed steps' counter "
+                         "rows, a seeded sample of the groups' state after the last step and the engine's digest")
     ap.add_argument("--groups", type=int, default=None,
                     help="total groups (strong scaling) or groups per GPU (weak scaling); default: the "
                          "configuration's own (BASELINE.json: 10^6 for config 3, 10^5 for 5, 10^4 for 2)")
@@ -320,10 +352,11 @@ def parse_args(argv=None):
                          "after the last launch, inside the timed region (end); per --reduce-every chunk, in series "
                          "with the launches (inline); or once the clock has stopped (after: a diagnostic that "
                          "leaves the collective off the clock)")
-    ap.add_argument("--kernel-timing", choices=["replay", "region"], default="replay",
+    ap.add_argument("--kernel-timing", choices=["replay", "region", "off"], default=None,
                     help="where the step kernel's per-launch time comes from: an exact replay of the timed launches "
-                         "after the clock, each launch carrying its own timestamps (replay), or the timed region's "
-                         "own launches (region: the timestamps are then inside the clock)")
+                         "after the clock, each launch carrying its own timestamps (replay, the default with "
+                         "--full), the timed region's own launches (region: the timestamps are then inside the "
+                         "clock), or nowhere (off, the default of a plain run: no kernel times and no rooflines)")
     ap.add_argument("--no-rehearse", dest="rehearse", action="store_false",
                     help="skip the untimed rehearsal of the timed launches (then raft_engine_reset) before the warmup")
     ap.add_argument("--rehearse-ms", type=float, default=50.0,
@@ -360,7 +393,41 @@ def parse_args(argv=None):
                     help="no GPU: start the ranks, agree on the shards over gloo, print them (tests)")
     args = ap.parse_args(argv)
     args.groups = abi.CONFIGS[args.config]["G"] if args.groups is None else args.groups
+    if args.kernel_timing is None:
+        args.kernel_timing = "replay" if args.full else "off"
     return args
+
+
+def dump_sample_runs(G: int) -> list[tuple[int, int]]:
+    """(first local group, groups) of the --dump-outputs state sample: every
+    group of a shard of at most DUMP_SAMPLE_GROUPS, else DUMP_SAMPLE_RUNS runs
+    of DUMP_SAMPLE_RUN consecutive groups at seeded, sorted, distinct offsets
+    (the same for every run with the same shard size)."""
+    if G <= DUMP_SAMPLE_GROUPS:
+        return [(0, G)]
+    rng = np.random.default_rng(DUMP_SEED)
+    first = np.sort(rng.choice(G // DUMP_SAMPLE_RUN, DUMP_SAMPLE_RUNS, replace=False)) * DUMP_SAMPLE_RUN
+    return [(int(g), DUMP_SAMPLE_RUN) for g in first]
+
+
+def dump_outputs(path: str, eng, rank: int, gcounters) -> dict:
+    """--dump-outputs: called once the clock has stopped, before anything else
+    touches the engine.  Returns the line's `outputs` object."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    runs = dump_sample_runs(eng.G)
+    state = np.concatenate([eng.read_state(g, n) for g, n in runs]).astype(np.float64)
+    d = eng.digest()
+    files = {f"state_sample{sfx}": state, f"digest{sfx}": np.array([d >> 32, d & 0xFFFFFFFF], dtype=np.float64)}
+    if rank == 0:
+        rows = gcounters.cpu().numpy()[:, : abi.NUM_COUNTERS].astype(np.float64)
+        files["counters"] = rows[-max(1, DUMP_COUNTER_BYTES // (8 * abi.NUM_COUNTERS)):]
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": {n + ".npy": list(a.shape) for n, a in files.items()}, "dtype": "float64",
+            "bytes": int(sum(a.nbytes for a in files.values())),
+            "state_sample": (f"{len(runs)} runs of {runs[0][1]} consecutive groups, seed {DUMP_SEED}"
+                             if len(runs) > 1 else "every group")}
 
 
 def rehearsal_count(rehearse_ms, groups, steps, coll=False, dev="cpu"):
@@ -376,7 +443,7 @@ def rehearsal_count(rehearse_ms, groups, steps, coll=False, dev="cpu"):
     return n
 
 
-def timed_leg(eng, args, chunk, coll, dev, world, comm=None):
+def timed_leg(eng, args, chunk, coll, dev, world, comm=None, after_clock=None):
     """Warmup (untimed), then the timed region of `args.steps` lockstep steps on
     `eng`: enqueued in chunks of `chunk` steps, bracketed by a barrier and a
     device sync on both sides.  When `coll`, the counter rows are all-reduced
@@ -388,7 +455,9 @@ def timed_leg(eng, args, chunk, coll, dev, world, comm=None):
     raft_engine_allreduce_counters, out of place; else torch.distributed's
     all_reduce after a row copy.  Returns this rank's clock, the
     stream-event, step-kernel and all-reduce times, the job's elapsed time (MAX
-    over ranks) and the counter rows (this rank's, all ranks', warmup)."""
+    over ranks) and the counter rows (this rank's, all ranks', warmup).
+    `after_clock(gcounters)` runs once the clock has stopped and every rank's
+    rows are summed, before the replay (--dump-outputs)."""
     import torch
     import torch.distributed as dist
     stream = torch.cuda.ExternalStream(eng.stream, device=dev)
@@ -447,10 +516,10 @@ def timed_leg(eng, args, chunk, coll, dev, world, comm=None):
     # ---- timed region ----
     # The launches' own start / stop timestamps (hipExtLaunchKernelGGL events)
     # cost ~10 us of host time at the first launch (profiles/r6_b shard_ab):
-    # by default (--kernel-timing replay) the timed region carries no event at
-    # all, and the kernel and all-reduce times come from an exact replay of
-    # the same launches after the clock (below); --kernel-timing region times
-    # the region's own.
+    # by default the timed region carries no event at all: with --full
+    # (--kernel-timing replay) the kernel and all-reduce times come from an
+    # exact replay of the same launches after the clock (below), a plain run
+    # (off) has none; --kernel-timing region times the region's own.
     # RAFT_BENCH_NO_KERNEL_EVENTS=1: no kernel times at all (A/B runs).
     no_ev = os.environ.get("RAFT_BENCH_NO_KERNEL_EVENTS") == "1"
     timing = args.kernel_timing == "region" and not no_ev
@@ -532,6 +601,8 @@ def timed_leg(eng, args, chunk, coll, dev, world, comm=None):
             dist.all_reduce(gcounters)
             torch.cuda.synchronize(dev)
             after_ms = (time.perf_counter() - t_ar) * 1e3
+    if after_clock is not None:
+        after_clock(gcounters)
     ev_ms = eng.timed_span(ev1.cuda_event) if timing else None
     allreduce_ms = ar0.elapsed_time(ar1) if mode == "end" and instr else (after_ms if mode == "after" else None)
     kern_ms, launches = eng.kernel_time()
@@ -662,7 +733,9 @@ def main(argv=None, result=None):
     eng = eng_mod.RaftEngine(params, device=local)
     nsub = eng.subranges                                     # launch sub-ranges of the warmup and timed legs
     hbm_bytes_engine = eng.device_bytes
-    leg = timed_leg(eng, args, chunk, coll, dev, world, comm)
+    outputs = {}
+    dump = (lambda rows: outputs.update(dump_outputs(args.dump_outputs, eng, rank, rows))) if args.dump_outputs else None
+    leg = timed_leg(eng, args, chunk, coll, dev, world, comm, after_clock=dump)
     wall, ev_ms, kern_ms, launches = leg["wall"], leg["ev_ms"], leg["kern_ms"], leg["launches"]
     elapsed, kern_avg_ms, kern_avg_per_rank = leg["elapsed"], leg["kern_avg_ms"], leg["kern_avg_per_rank"]
     counters, gcounters, wcount = leg["counters"], leg["gcounters"], leg["wcount"]
@@ -694,7 +767,8 @@ def main(argv=None, result=None):
                "kernel_src": kernel_source_id()}
     if args.ae_max_entries > 1:
         pmc_key["ae_max_entries"] = args.ae_max_entries
-    pmc = load_pmc(dict(pmc_key, leg="timed")) if len(set(timed_plan)) == 1 else None
+    # (a PMC row prices the launch's measured time: none without kernel times)
+    pmc = load_pmc(dict(pmc_key, leg="timed")) if launches and len(set(timed_plan)) == 1 else None
     traffic = pmc["hbm_bytes_per_launch"] if pmc else None
     roofline_valu = None
     if pmc and pmc.get("valu_per_launch"):
@@ -721,12 +795,13 @@ def main(argv=None, result=None):
     # ---- the general kernel (untimed for `value`): the warmup and timed legs
     # replayed from step 0, ending at the same state ----
     general = None
-    if world == 1 and not coll and not args.no_general_leg and net != abi.NET_ALL:
+    if args.full and world == 1 and not coll and not args.no_general_leg and net != abi.NET_ALL:
         general = legs().general_kernel_leg(eng, args, chunk, dev, c_loc, kern_avg_ms)
 
     # ---- streaming leg (untimed for `value`): one step per launch, the
     # HBM-bound formulation of the same step (bench_legs.streaming_leg) ----
-    streaming, bad_stream = legs().streaming_leg(eng, args, dev, G_local, R, pmc_key) if args.stream_steps > 0 else (None, 0)
+    streaming, bad_stream = (legs().streaming_leg(eng, args, dev, G_local, R, pmc_key)
+                             if args.full and args.stream_steps > 0 else (None, 0))
     bad_untimed += bad_stream
 
     # ---- traffic probes (untimed, --traffic-probe): the step kernel's own
@@ -752,7 +827,7 @@ def main(argv=None, result=None):
         if general is not None:                   # the general kernel runs the same leg from step 0
             seq += [["general" if x[0] == "general_timed" else x[0], *x[1:]]
                     for x in leg_seq("general_", general["rehearsals"])]
-        seq += [["streaming", 1, 1]] * args.stream_steps
+        seq += [["streaming", 1, 1]] * (args.stream_steps if args.full else 0)
         ix = abi.C_INDEX
         stores = float(c_loc[:, ix["entry_writes"]].sum() + c_loc[:, ix["commands"]].sum()) / max(1, launches)
         json.dump({"key": pmc_key, "stream_steps": args.stream_steps, "R": R, "launches": seq, "probes": probes,
@@ -762,11 +837,11 @@ def main(argv=None, result=None):
 
     # ---- safety flags (untimed): the run's counter-borne flags plus the
     # Log Matching check over committed prefixes ----
-    mism = eng.check_log_matching()
+    mism = eng.check_log_matching() if args.full else None      # a pass over every log: --full
     if coll:
-        t = torch.tensor([mism, bad_untimed], dtype=torch.int64, device=dev)
+        t = torch.tensor([mism or 0, bad_untimed], dtype=torch.int64, device=dev)
         dist.all_reduce(t)
-        mism, bad_untimed = int(t[0].item()), int(t[1].item())
+        mism, bad_untimed = int(t[0].item()) if args.full else None, int(t[1].item())
     safety = {
         "log_matching_mismatched_groups": mism,
         "commit_regressions": int(c_all[:, abi.C_INDEX["commit_regressions"]].sum()),
@@ -780,7 +855,7 @@ def main(argv=None, result=None):
 
     # the other scaling's leg: weak beside config 4 (the default), config 4 beside a weak job
     side = None
-    if world > 1 and args.config == 3 and not args.no_side_leg:
+    if args.full and world > 1 and args.config == 3 and not args.no_side_leg:
         eng.close()
         eng = None
         other = "weak" if args.scaling == "strong" else "strong"
@@ -796,6 +871,7 @@ def main(argv=None, result=None):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed * 1e3 / args.steps,
+        "full": args.full,
         "higher_is_better": True,
         "scaling": args.scaling,
         "vs_baseline": None,
@@ -814,7 +890,7 @@ def main(argv=None, result=None):
                         + (f", up to {args.ae_max_entries} entries per AppendEntries" if args.ae_max_entries > 1 else ""),
             "groups_total": total_groups, "groups_per_rank": groups_per_rank, "replicas": R, "log_cap": log_cap,
             "log_window": window, "hbm_bytes_engine": hbm_bytes_engine,
-            "steps_per_launch": L, "launches": launches, "parallelism": f"shard-by-group x{world}",
+            "steps_per_launch": L, "launches": launches or len(timed_plan), "parallelism": f"shard-by-group x{world}",
             "subranges": nsub,
             "step_waves_per_rank": -(-G_local // (64 // R)),
             "grid_fill": grid_fill(G_local, R, L, R <= 5 or (R == 7 and net == abi.NET_PART)),
@@ -865,9 +941,10 @@ def main(argv=None, result=None):
                    "replay_counters_equal": leg["replay_counters_equal"],
                    "rehearsals": leg["rehearsals"], "rehearse_ms": args.rehearse_ms,
                    "note": "each rank's wall clock from after the opening barrier + device sync to after its closing "
-                           "device sync (the job's time is the MAX over ranks); nothing inside it is instrumented "
-                           "(kernel_timing replay): the kernel and all-reduce times come from the same launches "
-                           "replayed from step 0 after the clock, whose counter rows equal the region's; before the "
+                           "device sync (the job's time is the MAX over ranks); nothing inside it is instrumented: "
+                           "with kernel_timing replay (--full) the kernel and all-reduce times come from the same "
+                           "launches replayed from step 0 after the clock, whose counter rows equal the region's, "
+                           "with kernel_timing off (a plain run) there are none; before the "
                            "warmup an untimed rehearsal of the timed launches (then a reset) runs for >= "
                            "--rehearse-ms, so the GPU leaves its idle clocks (DESIGN.md §5)"},
         "valid": overflow == 0 and wmiss == 0 and bad_untimed == 0,
@@ -876,10 +953,12 @@ def main(argv=None, result=None):
     }
     if side is not None:
         out["weak_scaling" if side["scaling"] == "weak" else "config4_strong"] = side
-    if args.handler_batch > 0 and world == 1 and not coll:
+    if outputs:
+        out["outputs"] = outputs
+    if args.full and args.handler_batch > 0 and world == 1 and not coll:
         out["handler_batch"] = legs().handler_batch_leg(eng, args, dict(kw, mode=mode, ae_max_entries=args.ae_max_entries),
                                                  log_cap, dev, G_local, R)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = legs().cpu_baseline(args, dict(kw, mode=mode, ae_max_entries=args.ae_max_entries), log_cap,
                                                   args.warmup + args.steps, device=local)
     if rank == 0:

@@ -11,7 +11,7 @@ for i in $(seq ${ROUNDS:-2}); do
     v=${spec%%:*}; k=""; [ "$spec" != "$v" ] && k="--steps-per-launch ${spec#*:}"
     lib=raft-kotlin_amd/lib/libraft_engine.so; [ "$v" != base ] && lib=raft-kotlin_amd/lib/libraft_engine_$v.so
     log="$OUT/${spec//:/_}_$i.log"
-    RAFT_ENGINE_LIB=$PWD/$lib timeout -k 10 200 python -u bench.py ${ARGS:---steps 10000} $k --no-cpu-baseline \
+    RAFT_ENGINE_LIB=$PWD/$lib timeout -k 10 200 python -u bench.py --full ${ARGS:---steps 10000} $k --no-cpu-baseline \
         --stream-steps 0 > "$log" 2>&1
     rc=$?; echo "$spec $i rc=$rc $(grep -o '"value": [0-9.e+]*' "$log") $(grep -o '"kernel_avg_ms": [0-9.]*' "$log" | head -1)" >> "$OUT/status.txt"
     [ $rc -ne 0 ] && exit $rc

@@ -8,11 +8,11 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 OUT=gpurun_out/${TAG:-dist}; mkdir -p "$OUT"
 S=${STEPS:-2048}
-timeout -k 10 300 python -u bench.py --steps $S --stream-steps 0 --no-cpu-baseline --handler-batch 0 \
+timeout -k 10 300 python -u bench.py --full --steps $S --stream-steps 0 --no-cpu-baseline --handler-batch 0 \
     > "$OUT/one_rank.log" 2>&1 || exit $?
-RAFT_BENCH_BACKEND=gloo RAFT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python -u bench.py --gpus 2 --steps $S \
+RAFT_BENCH_BACKEND=gloo RAFT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python -u bench.py --full --gpus 2 --steps $S \
     --stream-steps 0 --no-cpu-baseline > "$OUT/two_rank.log" 2>&1 || exit $?
-RAFT_BENCH_BACKEND=gloo RAFT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python -u bench.py --gpus 2 --steps $S \
+RAFT_BENCH_BACKEND=gloo RAFT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python -u bench.py --full --gpus 2 --steps $S \
     --stream-steps 0 --no-cpu-baseline --scaling weak > "$OUT/two_rank_weak.log" 2>&1 || exit $?
 grep '^{' "$OUT/two_rank_weak.log" | tail -1 > "$OUT/dist_rehearsal_2rank_weak_gloo_one_gpu.json"
 grep '^{' "$OUT/one_rank.log" | tail -1 > "$OUT/dist_rehearsal_1rank.json"

@@ -10,8 +10,8 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python -u -m pytest tests -m gpu -q -x --timeout 200 --timeout-method thread > "$OUT/pytest.log" 2>&1 || exit $?
 fi
 for i in $(seq 1 ${N:-3}); do
-  timeout -k 10 200 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/driver_$i.log" 2>&1 || exit $?
+  timeout -k 10 200 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/driver_$i.log" 2>&1 || exit $?
 done
-[ -n "$SKIP_DEFAULT" ] || { timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$OUT/default.log" 2>&1 || exit $?; }
+[ -n "$SKIP_DEFAULT" ] || { timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$OUT/default.log" 2>&1 || exit $?; }
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --stream-steps 0 > "$OUT/trace.log" 2>&1
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --stream-steps 0 > "$OUT/trace.log" 2>&1

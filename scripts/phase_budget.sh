@@ -12,7 +12,7 @@ A=${ARGS:-"--steps 20 --warmup 5"}
 for v in base ${VARIANTS:-tw_t tw_jobs tw_v tw_a tw_c}; do
   lib=$PWD/raft-kotlin_amd/lib/libraft_engine.so; [ "$v" != base ] && lib=$PWD/raft-kotlin_amd/lib/libraft_engine_$v.so
   RAFT_ENGINE_LIB=$lib timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS \
-      -d "$OUT/$v" -o run --output-format csv -- python bench.py $A --no-cpu-baseline --handler-batch 0 \
+      -d "$OUT/$v" -o run --output-format csv -- python bench.py --full $A --no-cpu-baseline --handler-batch 0 \
       --stream-steps 0 --no-general-leg > "$OUT/$v.log" 2>&1
   rc=$?; echo "$v rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || exit $rc
 done

@@ -17,7 +17,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_${TAG:-x}
 mkdir -p "$OUT"
-A="${ARGS:-} --no-cpu-baseline --traffic-probe --plan-file $OUT/plan.json"
+A="${ARGS:-} --full --no-cpu-baseline --traffic-probe --plan-file $OUT/plan.json"
 echo "trace" >> "$OUT/status.txt"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python bench.py $A > "$OUT/trace.log" 2>&1 || exit $?

@@ -7,7 +7,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-attrib}; mkdir -p "$OUT"
-A="${ARGS:---steps 2000 --warmup 0} --subranges 1 --stream-steps 0 --handler-batch 0 --no-cpu-baseline"
+A="${ARGS:---steps 2000 --warmup 0} --full --subranges 1 --stream-steps 0 --handler-batch 0 --no-cpu-baseline"
 for v in ${VARIANTS:-base sinkst sinkld sinkboth}; do
   lib=raft-kotlin_amd/lib/libraft_engine.so; [ "$v" != base ] && lib=raft-kotlin_amd/lib/libraft_engine_$v.so
   RAFT_ENGINE_LIB=$PWD/$lib timeout -k 10 200 python -u bench.py $A --plan-file "$OUT/plan_$v.json" > "$OUT/bench_$v.log" 2>&1

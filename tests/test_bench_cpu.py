@@ -161,6 +161,30 @@ def test_counter_allreduce_is_inside_the_timed_region_by_default():
     assert bench.parse_args(["--allreduce", "after"]).allreduce == "after"
 
 
+def test_plain_run_is_the_default_and_full_brings_the_replay():
+    """A plain run times only (no kernel-time replay); --full restores the
+    replay unless a --kernel-timing is asked for."""
+    plain, full = bench.parse_args([]), bench.parse_args(["--full"])
+    assert (plain.full, plain.kernel_timing, plain.dump_outputs) == (False, "off", "")
+    assert (full.full, full.kernel_timing) == (True, "replay")
+    assert bench.parse_args(["--full", "--kernel-timing", "region"]).kernel_timing == "region"
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+@pytest.mark.parametrize("G", [1, 4_097, 32_768, 32_769, 125_000, 1_000_000])
+def test_dump_sample_is_fixed_distinct_and_bounded(G):
+    """The --dump-outputs state sample: every group of a small shard, else
+    seeded disjoint runs inside the shard, the same on every call, within
+    64 MB as float64 beside the counter rows at the widest group (R = 8)."""
+    runs = bench.dump_sample_runs(G)
+    assert runs == bench.dump_sample_runs(G)
+    n = sum(k for _, k in runs)
+    assert n == min(G, bench.DUMP_SAMPLE_GROUPS)
+    assert all(0 <= g and g + k <= G for g, k in runs)
+    assert all(a[0] + a[1] <= b[0] for a, b in zip(runs, runs[1:]))
+    assert n * abi.group_words(abi.MAX_R) * 8 + bench.DUMP_COUNTER_BYTES + 16 <= 64_000_000
+
+
 def test_pmc_parse_probe_factors(tmp_path):
     """The byte factors come from the traffic probes of the same bench process:
     the state probe's known bytes over its FETCH_SIZE / WRITE_SIZE kilobytes,

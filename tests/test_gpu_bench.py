@@ -37,7 +37,8 @@ def test_forced_collective_at_one_rank(backend, mode, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     G, warm, steps = 24_000, 40, 800          # two 400-step launches: two all-reduce chunks at --reduce-every 400
     res = {}
-    argv = ["--groups", str(G), "--steps", str(steps), "--warmup", str(warm), "--stream-steps", "0",
+    # --full: the kernel-time replay and its rooflines are legs beside the timed region
+    argv = ["--full", "--groups", str(G), "--steps", str(steps), "--warmup", str(warm), "--stream-steps", "0",
             "--reduce-every", "400", "--no-cpu-baseline"] + (["--allreduce", mode] if mode else [])
     rc = bench.main(argv, result=res)
     assert rc == 0
@@ -64,6 +65,40 @@ def test_forced_collective_at_one_rank(backend, mode, monkeypatch):
     co = o.step(warm + steps, nthreads=min(16, os.cpu_count() or 1))[:, : abi.NUM_COUNTERS]
     assert np.array_equal(res["warmup_counters"], co[:warm])
     assert np.array_equal(ca, co[warm:]), "all-reduced counter rows differ from the oracle's"
+
+
+def test_plain_run_times_only_and_dumps_its_outputs(tmp_path, monkeypatch):
+    """A plain run (no --full) carries no leg beside the timed region, and
+    --dump-outputs writes what the region computed: the timed steps' counter
+    rows, the groups' state after the last step and the digest, all equal to
+    the oracle's for the same groups and steps."""
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RAFT_BENCH_FORCE_COLLECTIVE"):
+        monkeypatch.delenv(k, raising=False)
+    G, warm, steps = 3_001, 7, 45
+    res = {}
+    rc = bench.main(["--gpus", "1", "--groups", str(G), "--steps", str(steps), "--warmup", str(warm),
+                     "--dump-outputs", str(tmp_path)], result=res)
+    assert rc == 0
+    out = res["out"]
+    assert out["full"] is False and out["steps"] == steps and out["valid"] and out["value"] > 0
+    assert abs(out["ms_per_step"] - G * 1e3 / out["value"]) < 1e-9 * out["ms_per_step"]
+    for leg in ("general_kernel", "roofline_streaming", "roofline_valu"):
+        assert out[leg] is None
+    assert "cpu_baseline" not in out and "handler_batch" not in out
+    assert out["timing"]["kernel_timing"] == "off" and out["timing"]["replay_counters_equal"] is None
+    assert out["safety"]["log_matching_mismatched_groups"] is None
+    assert sorted(os.listdir(tmp_path)) == ["counters.npy", "digest.npy", "state_sample.npy"]
+    assert sorted(out["outputs"]["files"]) == sorted(os.listdir(tmp_path))
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("counters", "digest", "state_sample")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == out["outputs"]["bytes"] <= 64 << 20
+    o = O.Oracle(abi.make_params(log_cap=out["config"]["log_cap"], **dict(abi.CONFIGS[3], G=G)))
+    co = o.step(warm + steps, nthreads=min(16, os.cpu_count() or 1))[:, : abi.NUM_COUNTERS]
+    assert np.array_equal(got["counters"], co[warm:])
+    assert np.array_equal(got["counters"], res["counters_all"])
+    assert np.array_equal(got["state_sample"], o.read_state())
+    d = o.digest()
+    assert [int(x) for x in got["digest"]] == [d >> 32, d & 0xFFFFFFFF]
 
 
 def test_native_counter_allreduce_at_one_rank():
