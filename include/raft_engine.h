@@ -306,7 +306,8 @@ int raft_engine_kernel_time(raft_engine* e, double* total_ms, int64_t* launches)
  * its last launch); call before raft_engine_kernel_time, which resets the
  * timed launches. */
 int raft_engine_timed_span(raft_engine* e, void* end_event, double* ms);
-int64_t raft_engine_step_index(raft_engine* e);   /* steps executed so far */
+int64_t raft_engine_step_index(raft_engine* e);   /* the index of the next step: the steps executed so far
+                                                   * (from the index last set), mod 2^32 */
 /* Steps fused into one kernel launch from now on (0 = 1), at most
  * RAFT_MAX_STEPS_PER_LAUNCH.  Results do not depend on it. */
 int     raft_engine_set_steps_per_launch(raft_engine* e, int32_t k);
@@ -322,8 +323,11 @@ int     raft_engine_set_kernel(raft_engine* e, int32_t kernel);
  * raft_engine_create leaves it (RaftServer.kt:35-48, the election timers armed
  * as init does, :58). */
 int     raft_engine_reset(raft_engine* e);
-/* Set the index of the next step (its Philox counter c0); with write_state
- * this resumes a run exported at any step. */
+/* Set the index of the next step (its Philox counter c0), 0 <= t < 2^32; with
+ * write_state, then write_log, this resumes a run exported at any step.  The
+ * index is a 32-bit counter: a run that steps past 2^32 - 1 goes on at 0 (the
+ * harness draws, `t % partition_period` and a partition window's first step
+ * are all taken in uint32_t), and raft_engine_step_index reports it mod 2^32. */
 int     raft_engine_set_step_index(raft_engine* e, int64_t t);
 /* HBM owned by the engine: the state, logs and counter buffers, plus the
  * grow-only staging of the handler batches and accessors (kept for the

@@ -1478,7 +1478,7 @@ int raft_engine_step_async(raft_engine* e, int32_t n_steps, int64_t* counters_de
         done += k;
     }
     HIP_TRY(hipGetLastError());
-    e->t += (uint64_t)n_steps;
+    e->t = (uint32_t)(e->t + (uint64_t)n_steps);   // the step index is a 32-bit counter (the Philox c0): it wraps
     return RAFT_OK;
 }
 

@@ -70,6 +70,60 @@ def assert_same_logs(a_state, a_logs, b_logs, R, label=""):
         raise AssertionError(f"{label}: {len(bad)} log slots differ; first {bad[0].tolist()}")
 
 
+# ---- the parameter corners (test_gpu_param_edges.py, test_param_edges_cpu.py) ----
+
+# drops, isolation churn, partitions and commands at once (test_other_replica_counts)
+STRESS_MIX = dict(drop_ppm=100_000, churn_ppm=20_000, churn_steps=15, cmd_ppm=500_000,
+                  partition_period=40, partition_len=10)
+
+# Philox keys with a high word: all 64 bits set about, and two seeds that share key0
+SEEDS64 = [0x9E3779B97F4A7C15, (0x9E3779B9 << 32) | 7, 7]
+
+
+def _timers(hb, emin, emax, bmin, bmax, rto, retry):
+    return dict(heartbeat_ms=hb, election_min_ms=emin, election_max_ms=emax, backoff_min_ms=bmin,
+                backoff_max_ms=bmax, round_timeout_ms=rto, retry_ms=retry)
+
+
+TIMER_SETS = {
+    "odd": _timers(1500, 7000, 9500, 1000, 4000, 11000, 3500),       # nothing is a multiple of the heartbeat
+    "fast": _timers(1000, 3000, 3001, 1, 999, 2500, 1000),           # a two-value range; backoff ends inside a step
+    "wide": _timers(700, 1, 60000, 0, 20000, 9000, 1),               # scale_range over a wide range; retry every step
+    "slowhb": _timers(5000, 6000, 6000, 7000, 7000, 4999, 12000),    # round over before a tick; retry outlasts it
+}
+# the reference's constants with no backoff, an immediate round timeout and an immediate retry
+DEGENERATE_TIMERS = dict(backoff_min_ms=0, backoff_max_ms=0, round_timeout_ms=0, retry_ms=0)
+
+# overrides of STRESS_MIX at the ends of the fault rates: hit16's threshold is
+# ceil(ppm * 2^16 / 10^6), so 1 and 15 ppm share threshold 1, 16 ppm is 2 and
+# 10^6 ppm is 65,536 (beyond 16 bits); 10^6 ppm of churn is 2^32
+FAULT_EDGES = {
+    "drop1": dict(drop_ppm=1), "drop15": dict(drop_ppm=15), "drop16": dict(drop_ppm=16),
+    "dropall": dict(drop_ppm=1_000_000),
+    "churnall": dict(churn_ppm=1_000_000, churn_steps=3),
+    "part7of7": dict(partition_period=7, partition_len=7),           # always partitioned
+    "part9of5": dict(partition_period=5, partition_len=9),           # the length exceeds the period
+    "part1of1": dict(partition_period=1, partition_len=1),           # redrawn every step
+}
+
+
+def high_g0(G: int) -> dict:
+    """Shards of G groups at the top of the 32-bit global ids: the last group
+    is 2^32 - 1, and a shard that straddles bit 31."""
+    return {"top": (1 << 32) - G, "bit31": (1 << 31) - G // 2}
+
+
+def assert_not_vacuous(counters: np.ndarray, kw: dict, label: str = ""):
+    """The run elected leaders, took and committed commands, lost messages
+    where a fault is configured, and never overflowed its log_cap: a condition
+    on a test's inputs (checked on the oracle's counter rows), not a tolerance."""
+    tot = {n: int(counters[:, i].sum()) for n, i in abi.C_INDEX.items()}
+    assert tot["leaders_elected"] > 0 and tot["commits"] > 0 and tot["commands"] > 0, (label, tot)
+    if kw.get("drop_ppm") or kw.get("churn_ppm") or (kw.get("partition_period") and kw.get("partition_len")):
+        assert tot["msg_dropped"] > 0, (label, tot)
+    assert tot["log_overflow"] == 0, (label, tot)
+
+
 def log_matching_flags(state: np.ndarray, terms: np.ndarray, cmds: np.ndarray, R: int, window: int = 0) -> np.ndarray:
     """Per group: 1 if two replicas differ at an index inside both committed
     prefixes (i < min(commitIndex, lastIndex) of each) and, with a log_window
