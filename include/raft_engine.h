@@ -42,7 +42,9 @@ extern "C" {
 
 /* 2: raft_params.schedule / schedule_workgroups / kernel, automatic
  * subranges by workload (1 or 3), raft_engine_kernel_info, raft_engine_set_kernel,
- * raft_engine_reset, raft_engine_wait_stream */
+ * raft_engine_reset, raft_engine_wait_stream.  Added since without a new
+ * version, because nothing that existed changed: committed-entry delivery
+ * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -329,8 +331,8 @@ int     raft_engine_reset(raft_engine* e);
  * harness draws, `t % partition_period` and a partition window's first step
  * are all taken in uint32_t), and raft_engine_step_index reports it mod 2^32. */
 int     raft_engine_set_step_index(raft_engine* e, int64_t t);
-/* HBM owned by the engine: the state, logs and counter buffers, plus the
- * grow-only staging of the handler batches and accessors (kept for the
+/* HBM owned by the engine: the state, logs, counter buffers and lastApplied,
+ * plus the grow-only staging of the handler batches, accessors and drains (kept for the
  * engine's lifetime at 1.25x the largest request; raft_engine_trim_staging
  * frees it, page-locked host staging included). */
 /* ---- multi-GPU: the counter all-reduce ----------------
@@ -396,6 +398,73 @@ int raft_engine_digest_range(raft_engine* e, int64_t g0, int64_t n, uint64_t* ou
  * error.  *mismatched = flagged groups; flags (nullable, host, n bytes)
  * receives 1 per flagged group. */
 int raft_engine_check_log_matching(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, int64_t* mismatched);
+
+/* ---- committed-entry delivery: lastApplied and the apply stream ----------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed;
+ * a host built against the earlier header runs unchanged).
+ *
+ * The reference declares lastApplied (RaftServer.kt:47) and never uses it.
+ * Here it is a count per replica, like commitIndex: entries [0, lastApplied)
+ * of that replica's log have been delivered to the caller.  It lives in an
+ * array of its own: it is not part of the canonical state, of read_state /
+ * write_state or of the digest, the step kernel never touches it, and
+ * raft_engine_create / raft_engine_reset zero it.
+ *
+ * A drain visits the selected replicas of groups [g0, g0 + n): every replica
+ * (replica = -1) or replica index `replica` of each group.  For each, with
+ *   hi = clamp(min(commitIndex, lastIndex), 0, log_cap)   (the committed prefix of
+ *                                                          raft_engine_check_log_matching)
+ *   lo = lastApplied
+ * - with a log_window W and wl = max(0, physLen - W): if wl > lo and hi > lo,
+ *   the min(wl, hi) - lo entries below the window are gone; they are counted
+ *   in `lost`, lo moves past them, and the call returns RAFT_EWINDOW after
+ *   doing everything else (as the handler batches do);
+ * - if hi < lo (the reference's Q4 clamp can lower commitIndex, an overwrite
+ *   can shorten the log) the replica is counted in `regressed`, delivers
+ *   nothing and keeps its lastApplied: lastApplied never decreases;
+ * - else entries lo .. hi - 1 are delivered, one record each.
+ * Records come in ascending (group, replica, index) order.  When there are
+ * more than max_entries, exactly the first max_entries of that order are
+ * written, lastApplied advances only past what was written (the cut may fall
+ * inside one replica's run) and `pending` counts the rest: successive drains
+ * concatenated equal one drain with enough room.  out == NULL with
+ * max_entries == 0 is a peek: nothing is stored, not even the ring skip, and
+ * pending / lost / regressed report what a drain would see.
+ *
+ * Not promised: in RAFT_MODE_REFERENCE a delivered entry may later be
+ * overwritten in the log (quirks Q1-Q4, Q9), and two replicas of one group
+ * may deliver different streams.  In RAFT_MODE_TEXTBOOK the streams of a
+ * group's replicas are prefixes of one another.
+ *
+ * Ordering: the call runs on the engine stream; it sees every step enqueued
+ * before it and later step launches wait for it.  The host variant returns
+ * after the copy; the _dev variant (out: a DEVICE pointer to max_entries
+ * records, 8-byte aligned; info stays a host pointer) returns after its
+ * kernels finished. */
+typedef struct raft_applied_entry {   /* 24 bytes */
+    int64_t  group;                   /* engine-local group index */
+    int32_t  replica;
+    int32_t  index;                   /* log index i; committed when i < min(commitIndex, lastIndex) */
+    int32_t  term;
+    uint32_t cmd;
+} raft_applied_entry;
+typedef struct raft_drain_info {      /* 32 bytes */
+    int64_t delivered;   /* records written to out */
+    int64_t pending;     /* committed, undelivered entries left for lack of room (or all of them, in a peek) */
+    int64_t lost;        /* log_window only: entries that left the window undelivered; skipped */
+    int64_t regressed;   /* selected replicas whose min(commit, last) < lastApplied */
+} raft_drain_info;
+/* RAFT_EINVAL: null engine or info, replica outside -1..R-1, max_entries < 0,
+ * out == NULL with max_entries > 0; RAFT_ERANGE: groups outside the engine. */
+int raft_engine_drain_committed(raft_engine* e, int64_t g0, int64_t n, int32_t replica,
+                                raft_applied_entry* out_host, int64_t max_entries, raft_drain_info* info);
+int raft_engine_drain_committed_dev(raft_engine* e, int64_t g0, int64_t n, int32_t replica,
+                                    raft_applied_entry* out_dev, int64_t max_entries, raft_drain_info* info);
+/* lastApplied of groups [g0, g0 + n): [n][R] int32.  write_applied resumes a
+ * consumer (with write_state / write_log); every value must be in
+ * 0..log_cap, else RAFT_EINVAL and nothing is stored. */
+int raft_engine_read_applied(raft_engine* e, int64_t g0, int64_t n, int32_t* out);
+int raft_engine_write_applied(raft_engine* e, int64_t g0, int64_t n, const int32_t* in);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

@@ -175,6 +175,20 @@ class raft_append_resp(C.Structure):
     _fields_ = [("term", C.c_int32), ("success", C.c_int32), ("status", C.c_int32)]
 
 
+class raft_applied_entry(C.Structure):
+    _fields_ = [("group", C.c_int64), ("replica", C.c_int32), ("index", C.c_int32), ("term", C.c_int32),
+                ("cmd", C.c_uint32)]
+
+
+class raft_drain_info(C.Structure):
+    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("lost", C.c_int64), ("regressed", C.c_int64)]
+
+
+# raft_applied_entry as a numpy record (24 bytes, no padding)
+APPLIED_DTYPE = np.dtype([("group", np.int64), ("replica", np.int32), ("index", np.int32), ("term", np.int32),
+                          ("cmd", np.uint32)])
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -313,6 +327,10 @@ def load_library(path: str | None = None):
         "raft_engine_digest_range": (C.c_int, [eng, I64, I64, P(U64)]),
         "raft_engine_check_log_matching": (C.c_int, [eng, I64, I64, P(C.c_uint8), P(I64)]),
         "raft_engine_traffic_probe": (C.c_int, [eng, I32, P(I64), P(I64)]),
+        "raft_engine_drain_committed": (C.c_int, [eng, I64, I64, I32, C.c_void_p, I64, P(raft_drain_info)]),
+        "raft_engine_drain_committed_dev": (C.c_int, [eng, I64, I64, I32, C.c_void_p, I64, P(raft_drain_info)]),
+        "raft_engine_read_applied": (C.c_int, [eng, I64, I64, P(I32)]),
+        "raft_engine_write_applied": (C.c_int, [eng, I64, I64, P(I32)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -364,6 +382,7 @@ EXPORTED_SYMBOLS = [
     "raft_engine_device_bytes",
     "raft_engine_read_state", "raft_engine_write_state", "raft_engine_read_log",
     "raft_engine_write_log", "raft_engine_digest", "raft_engine_digest_range", "raft_engine_check_log_matching", "raft_engine_traffic_probe",
+    "raft_engine_drain_committed", "raft_engine_drain_committed_dev", "raft_engine_read_applied", "raft_engine_write_applied",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

@@ -1207,6 +1207,11 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     e->bflags_host = nullptr;
     e->aux = nullptr;
     e->aux_bytes = 0;
+    e->applied = nullptr;
+    e->apl = e->apo = nullptr;
+    e->applied_bytes = e->apl_bytes = e->apo_bytes = 0;
+    for (hipEvent_t& x : e->ev_drain) x = nullptr;
+    e->drain_timing = e->drain_expanded = false;
     e->hpart = nullptr;
     e->hpart_bytes = 0;
     e->device = device;
@@ -1268,6 +1273,16 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
         delete e;
         return fail(RAFT_ENOMEM, "hipMalloc of " + std::to_string(e->bytes) + " bytes failed");
     }
+    // lastApplied: an allocation of its own, outside the state the step kernel, the export and the digest see
+    e->applied_bytes = al((size_t)G * R * 4);
+    err = hipMalloc((void**)&e->applied, e->applied_bytes);
+    if (err != hipSuccess) {
+        e->applied_bytes = 0;
+        (void)hipFree(e->base);
+        (void)hipStreamDestroy(e->stream);
+        delete e;
+        return fail(RAFT_ENOMEM, "hipMalloc of lastApplied failed");
+    }
     char* b = (char*)e->base;
     d.st = (int32_t*)b; b += al(st_b);
     d.spill = (int32_t*)b; b += al(spill_b);
@@ -1298,8 +1313,10 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     }
     dispatch_R<InitL>(p->R, e);
     err = hipMemsetAsync(e->accum, 0, acc_b, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(e->applied, 0, e->applied_bytes, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (err != hipSuccess) {
+        (void)hipFree(e->applied);
         (void)hipFree(e->base);
         (void)hipStreamDestroy(e->stream);
         delete e;
@@ -1372,6 +1389,11 @@ int raft_engine_destroy(raft_engine* e) {
     if (e->hst) (void)hipHostFree(e->hst);
     if (e->bflags_host) (void)hipHostFree(e->bflags_host);
     if (e->aux) (void)hipFree(e->aux);
+    if (e->applied) (void)hipFree(e->applied);
+    if (e->apl) (void)hipFree(e->apl);
+    if (e->apo) (void)hipFree(e->apo);
+    for (hipEvent_t x : e->ev_drain)
+        if (x) (void)hipEventDestroy(x);
     if (e->hpart) (void)hipFree(e->hpart);
     (void)hipFree(e->base);
     (void)hipStreamDestroy(e->stream);
@@ -1623,6 +1645,7 @@ int raft_engine_reset(raft_engine* e) {
     for (int q = 0; q < e->nsub && e->nsub > 1; ++q) HIP_TRY(hipStreamSynchronize(e->sub_stream[q]));
     dispatch_R<InitL>(e->p.R, e);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(e->applied, 0, e->applied_bytes, e->stream));   // nothing delivered yet
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->bflags_host[8] = 0u;                // the step kernel's status word
     e->t = 0;
@@ -1663,7 +1686,9 @@ int raft_engine_set_step_index(raft_engine* e, int64_t t) {
     return RAFT_OK;
 }
 int64_t raft_engine_device_bytes(raft_engine* e) {
-    return e ? (int64_t)(e->bytes + e->bst_bytes + e->bio_bytes + e->aux_bytes + e->hpart_bytes) : -1;
+    return e ? (int64_t)(e->bytes + e->bst_bytes + e->bio_bytes + e->aux_bytes + e->hpart_bytes + e->applied_bytes +
+                         e->apl_bytes + e->apo_bytes)
+             : -1;
 }
 int raft_engine_trim_staging(raft_engine* e) {
     if (!e) return fail(RAFT_EINVAL, "null engine");
@@ -1673,8 +1698,10 @@ int raft_engine_trim_staging(raft_engine* e) {
     if (e->bio) HIP_TRY(hipFree(e->bio));
     if (e->aux) HIP_TRY(hipFree(e->aux));
     if (e->hst) HIP_TRY(hipHostFree(e->hst));
-    e->bst = e->bio = e->aux = e->hst = nullptr;
-    e->bst_bytes = e->bio_bytes = e->aux_bytes = e->hst_bytes = 0;
+    if (e->apl) HIP_TRY(hipFree(e->apl));
+    if (e->apo) HIP_TRY(hipFree(e->apo));
+    e->bst = e->bio = e->aux = e->hst = e->apl = e->apo = nullptr;
+    e->bst_bytes = e->bio_bytes = e->aux_bytes = e->hst_bytes = e->apl_bytes = e->apo_bytes = 0;
     return RAFT_OK;
 }
 

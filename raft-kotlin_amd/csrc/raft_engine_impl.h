@@ -1,6 +1,7 @@
 // raft_engine_impl.h — internal to the engine library: what raft_engine.hip
-// (the step kernel, the accessors, the C-ABI) and raft_batch.hip (the handler
-// batches, include/raft_engine.h raft_*_batch*) share -- the engine object, the
+// (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
+// batches, include/raft_engine.h raft_*_batch*) and raft_apply.hip (the
+// committed-entry drain) share -- the engine object, the
 // HBM indexing helpers and the error / staging entry points.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,6 +100,17 @@ struct raft_engine {
     int batch_path;             // RAFT_BATCH_PATH_* (raft_engine_set_batch_path)
     char* aux;                  // device staging of the state / log / digest accessors, grow-only
     size_t aux_bytes;
+    // committed-entry delivery (raft_apply.hip): lastApplied per replica [G * R], an allocation of its own
+    // (never part of the state export or the digest), and the drain's grow-only staging: counts, offsets
+    // and scan scratch (apl), the device copy of a host drain's records (apo)
+    int32_t* applied;
+    size_t applied_bytes;
+    char* apl;
+    size_t apl_bytes;
+    char* apo;
+    size_t apo_bytes;
+    hipEvent_t ev_drain[5];     // pass boundaries of the last drain while drain_timing (scripts/drain_probe.py)
+    bool drain_timing, drain_expanded;
     int64_t* counters_dev;      // [K][STRIDE] scratch
     unsigned long long* accum;  // [K * NC] counter accumulators: sum + chunks done << 48 (zero between launches)
     // step-kernel event timing

@@ -244,6 +244,87 @@ class RaftEngine:
                                                              C.byref(out)), "check_log_matching")
         return (int(out.value), f) if flags else int(out.value)
 
+    # -- committed-entry delivery (lastApplied, RaftServer.kt:47) ------------
+    def _drain_args(self, g0, n, replica, max_entries, what: str):
+        """The drain's arguments, checked before any library call."""
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n), ("replica", replica)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
+        if not -1 <= replica < self.R:
+            raise ValueError(f"{what}: replica {replica} must be -1 (all) or in 0..{self.R - 1}")
+        if max_entries is not None and (not isinstance(max_entries, (int, np.integer)) or max_entries < 0):
+            raise ValueError(f"{what}: max_entries must be None or an integer >= 0, not {max_entries!r}")
+        return int(g0), int(n), int(replica)
+
+    def _drain(self, fn, g0, n, replica, out_ptr, room, what: str) -> dict:
+        """One drain call.  RAFT_EWINDOW is not raised: the call did everything
+        else, so the records are returned and info["status"] carries the code
+        (info["lost"] > 0 says how many entries left the log window unread)."""
+        di = abi.raft_drain_info()
+        rc = fn(self._h, g0, n, replica, C.c_void_p(out_ptr or 0), int(room), C.byref(di))
+        if rc != abi.RAFT_EWINDOW:
+            self._check(rc, what)
+        return {"delivered": int(di.delivered), "pending": int(di.pending), "lost": int(di.lost),
+                "regressed": int(di.regressed), "status": int(rc)}
+
+    def peek_committed(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
+        """What a drain would see, storing nothing: info with delivered = 0 and
+        pending = every committed, undelivered entry of the selection."""
+        g0, n, replica = self._drain_args(g0, n, replica, None, "peek_committed")
+        return self._drain(self._lib.raft_engine_drain_committed, g0, n, replica, 0, 0, "peek_committed")
+
+    def drain_committed(self, g0: int = 0, n: int | None = None, replica: int = -1,
+                        max_entries: int | None = None):
+        """The entries of groups [g0, g0 + n) (replica -1: every replica, else
+        that replica index) that became committed since they were last drained:
+        (records, info).  records is a numpy array of abi.APPLIED_DTYPE (group,
+        replica, index, term, cmd) in ascending (group, replica, index) order,
+        at most max_entries of them (None: as many as there are -- a peek sizes
+        the buffer); lastApplied advances past what was returned.  info:
+        delivered, pending, lost, regressed, status (include/raft_engine.h)."""
+        g0, n, replica = self._drain_args(g0, n, replica, max_entries, "drain_committed")
+        if max_entries is None:
+            max_entries = self.peek_committed(g0, n, replica)["pending"]
+        # room 0 with a buffer is a drain (it stores the ring skip), not a peek: never a null buffer
+        out = np.zeros(max(1, int(max_entries)), dtype=abi.APPLIED_DTYPE)
+        info = self._drain(self._lib.raft_engine_drain_committed, g0, n, replica, out.ctypes.data, int(max_entries),
+                           "drain_committed")
+        return out[: info["delivered"]], info
+
+    def drain_committed_dev(self, out_ptr: int, max_entries: int, g0: int = 0, n: int | None = None,
+                            replica: int = -1, after_stream: int | None = None) -> dict:
+        """drain_committed into a DEVICE buffer of max_entries 24-byte records
+        (e.g. a torch uint8 tensor's data_ptr() on this engine's GPU; 8-byte
+        aligned); returns info once the kernels finished."""
+        g0, n, replica = self._drain_args(g0, n, replica, max_entries, "drain_committed_dev")
+        if max_entries is None or (max_entries > 0 and not out_ptr):
+            raise ValueError("drain_committed_dev: a device buffer and its max_entries are required")
+        if out_ptr % 8:
+            raise ValueError("drain_committed_dev: the record buffer must be 8-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._drain(self._lib.raft_engine_drain_committed_dev, g0, n, replica, out_ptr, max_entries,
+                           "drain_committed_dev")
+
+    def applied(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """lastApplied of groups [g0, g0 + n): [n, R] int32."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(n, 0), self.R), dtype=np.int32)          # a bad range is the library's to refuse
+        self._check(self._lib.raft_engine_read_applied(self._h, g0, n, abi.ptr(out, C.c_int32)), "read_applied")
+        return out
+
+    def set_applied(self, applied: np.ndarray, g0: int = 0):
+        """Store lastApplied of groups [g0, g0 + len(applied)) (resuming a
+        consumer): an integer [n, R] array with every value in 0..log_cap."""
+        a = np.asarray(applied)
+        if a.ndim != 2 or a.shape[1] != self.R or a.dtype.kind not in "iu":
+            raise ValueError(f"set_applied: applied {a.shape} {a.dtype} must be an integer array of shape (n, {self.R})")
+        if a.size and (a.min() < 0 or a.max() > self.cap):
+            raise ValueError(f"set_applied: every value must be in 0..{self.cap}")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        self._check(self._lib.raft_engine_write_applied(self._h, g0, a.shape[0], abi.ptr(a, C.c_int32)), "write_applied")
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

@@ -13,6 +13,8 @@ argument meaning and error behaviour:
 * ``appendCommand(command: str) -> str``                 (RaftServer.kt:100-107)
 * ``entries() -> list[str]`` in the reference's ``"term: command"`` format
   (RaftServer.kt:96-97)
+* ``lastApplied`` (RaftServer.kt:47) and ``RaftService.poll_committed``: the
+  entries that became committed since the last poll, for a state machine to apply
 
 Commands are strings in the reference (LogEntry.command, greeter.proto:31); the
 engine stores a u32 id per entry, interned here.  Every call is one HIP batch;
@@ -140,6 +142,11 @@ class RaftNode:
     def commitIndex(self) -> int:
         return int(self._fields()[abi.F_INDEX["commit"]])
 
+    @property
+    def lastApplied(self) -> int:                         # RaftServer.kt:47 (declared there, never used)
+        """Entries [0, lastApplied) of this node's log were handed out by poll_committed."""
+        return int(self.s.engine.applied(self.group, 1)[0, self.replica])
+
 
 class RaftService:
     """The `service Raft` surface of every node of a RaftEngine."""
@@ -173,6 +180,20 @@ class RaftService:
                 raise IndexError("Log.get: prevLogIndex out of bounds (RaftServer.kt:276, Commons.kt:53-54)")
             res.append(ResponseAppendEntriesRPC(int(t), bool(s)))
         return res
+
+    def poll_committed(self, g0: int = 0, n: Optional[int] = None, replica: int = -1,
+                       max_entries: Optional[int] = None):
+        """The apply loop's input: yields (group, replica, index, term, command)
+        for every entry of groups [g0, g0 + n) that became committed since the
+        last poll, in ascending (group, replica, index) order, and advances
+        lastApplied past them (one drain_committed call: no whole-log copy).
+        ``last_poll`` keeps that call's info (pending, lost, regressed)."""
+        # the drain runs now, not at the first next(): the returned iterator only decodes
+        rec, self.last_poll = self.engine.drain_committed(g0, n, replica, max_entries)
+        name = self.commands.name
+        return ((g, r, i, t, name(c)) for g, r, i, t, c in
+                zip(rec["group"].tolist(), rec["replica"].tolist(), rec["index"].tolist(), rec["term"].tolist(),
+                    rec["cmd"].tolist()))
 
     # -- the gRPC-facing wire form (include/raft_wire.h) --------------------
     # RaftImplBase.vote()/append() (RaftServer.kt:228, :253) receive and return
