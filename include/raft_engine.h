@@ -44,7 +44,8 @@ extern "C" {
  * subranges by workload (1 or 3), raft_engine_kernel_info, raft_engine_set_kernel,
  * raft_engine_reset, raft_engine_wait_stream.  Added since without a new
  * version, because nothing that existed changed: committed-entry delivery
- * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied) */
+ * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied) and the
+ * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -332,7 +333,7 @@ int     raft_engine_reset(raft_engine* e);
  * are all taken in uint32_t), and raft_engine_step_index reports it mod 2^32. */
 int     raft_engine_set_step_index(raft_engine* e, int64_t t);
 /* HBM owned by the engine: the state, logs, counter buffers and lastApplied,
- * plus the grow-only staging of the handler batches, accessors and drains (kept for the
+ * plus the grow-only staging of the handler batches, accessors, drains and client path (kept for the
  * engine's lifetime at 1.25x the largest request; raft_engine_trim_staging
  * frees it, page-locked host staging included). */
 /* ---- multi-GPU: the counter all-reduce ----------------
@@ -465,6 +466,102 @@ int raft_engine_drain_committed_dev(raft_engine* e, int64_t g0, int64_t n, int32
  * 0..log_cap, else RAFT_EINVAL and nothing is stored. */
 int raft_engine_read_applied(raft_engine* e, int64_t g0, int64_t n, int32_t* out);
 int raft_engine_write_applied(raft_engine* e, int64_t g0, int64_t n, const int32_t* in);
+
+/* ---- the client path: leader directory, routed proposals, tickets --------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The reference's client talks to one node's /cmd/{command} route
+ * (RaftServer.kt:87-88), which calls appendCommand (:100-107) on that node,
+ * leader or not, and learns nothing about the entry.  Here a client names a
+ * group: raft_propose_batch finds the group's leader on the device, runs
+ * appendCommand there and returns a ticket (where the entry went);
+ * raft_engine_resolve_tickets says later whether that entry is committed,
+ * still pending or lost; raft_engine_drain_committed hands the committed
+ * entries out.  The canonical state, the digest and the handler batches are
+ * untouched by all of this.
+ *
+ * raft_engine_read_leaders: one 16-byte record per group of [g0, g0 + n), read
+ * from the replicas' role words (no whole-state copy).  RAFT_ERANGE: groups
+ * outside the engine; RAFT_EINVAL: null engine, or null out_host with n > 0. */
+typedef struct raft_leader_info {   /* 16 bytes */
+    int32_t leader;     /* lowest replica index whose role is LEADER (RAFT_CMD_LOWEST_LEADER's choice), -1 if none */
+    int32_t term;       /* that replica's currentTerm, 0 if none */
+    int32_t n_leaders;  /* replicas with role LEADER */
+    int32_t commit;     /* that replica's commitIndex, 0 if none */
+} raft_leader_info;
+int raft_engine_read_leaders(raft_engine* e, int64_t g0, int64_t n, raft_leader_info* out_host);
+
+/* Propose: message m asks for cmd[m] to be replicated in group[m].
+ * - Messages apply in batch order.
+ * - A group's leader (raft_leader_info.leader) is looked up in the state the
+ *   call finds; appendCommand never changes a role, so every message to one
+ *   group goes to the same replica, and the k-th accepted message to a group
+ *   gets that leader's lastIndex + k.
+ * - The effect on state, logs and the log-tail cache is exactly that of
+ *   raft_append_command_batch called with those replicas on the messages that
+ *   found a leader (the same appendCommand, raft_step.h); a message without a
+ *   leader changes nothing.
+ * - A group outside the engine fails the whole batch with RAFT_ERANGE before
+ *   anything is applied (no ticket is written).  n == 0 is RAFT_OK.  n < 2^31.
+ * - With a log_window, a RAFT_MODE_TEXTBOOK add below its replica's window
+ *   returns RAFT_EWINDOW after applying the batch, as the handler batches do.
+ * - Ordering: the call runs on the engine stream (after rebuilding a stale
+ *   log-tail cache), later step launches wait for it, and it returns when the
+ *   batch has finished.  The _dev form takes DEVICE pointers under the buffer
+ *   rules of raft_*_batch_dev; ticket must be 16-byte aligned.
+ * RAFT_EINVAL: null engine, n < 0 or n >= 2^31, a null buffer with n > 0. */
+#define RAFT_PROPOSE_ACCEPTED  0  /* stored; log[index] of `replica` is (term, cmd) */
+#define RAFT_PROPOSE_GHOSTED   1  /* reference mode only, quirk Q1: physLen != lastIndex before the add, so
+                                     log.add stored the entry at the physical end and log[index] shows the
+                                     stale slot; lastIndex still grew by one */
+#define RAFT_PROPOSE_NO_LEADER 2  /* no replica of the group is LEADER: nothing appended */
+#define RAFT_PROPOSE_LOG_FULL  3  /* the leader's Log.add was refused for lack of physical capacity */
+typedef struct raft_ticket {      /* 16 bytes */
+    int32_t replica;   /* the leader chosen, -1 for NO_LEADER */
+    int32_t index;     /* the leader's lastIndex before the add (where the entry went / would have gone), -1 for NO_LEADER */
+    int32_t term;      /* the leader's currentTerm = the entry's term, 0 for NO_LEADER */
+    int32_t status;    /* RAFT_PROPOSE_* */
+} raft_ticket;
+int raft_propose_batch    (raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int64_t n);
+int raft_propose_batch_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int64_t n);
+
+/* Resolve: what became of the entry ticket[m] names in group[m] (cmd[m]: the
+ * command that was proposed).  Read-only; every record is filled.
+ * - A group outside the engine: RAFT_TICKET_INVALID, counts 0.
+ * - Else a ticket with status NO_LEADER or LOG_FULL: RAFT_TICKET_NONE, counts 0.
+ * - Else a ticket with replica outside -1..R-1 or index outside
+ *   0..log_cap-1: RAFT_TICKET_INVALID, counts 0.
+ * - Else slot `index` of every replica of the group is looked up (holders,
+ *   committed_on, unknown below; a replica counted in unknown is not read and
+ *   is no holder) and the status is COMMITTED if
+ *   committed_on >= 1, otherwise UNKNOWN if unknown >= 1, otherwise PENDING if
+ *   the ticket's own replica is a holder, otherwise LOST.  A GHOSTED ticket
+ *   gets no special case: it is looked up like any other and is normally LOST
+ *   at once.
+ * Returns RAFT_ERANGE if any group was out of range, otherwise RAFT_EINVAL if
+ * any ticket had a bad replica or index (also: null engine, n < 0 or n >= 2^31,
+ * a null buffer with n > 0, and then nothing is filled), otherwise
+ * RAFT_EWINDOW if any record is UNKNOWN, otherwise RAFT_OK.
+ * Not promised: in RAFT_MODE_REFERENCE a COMMITTED entry can later turn LOST
+ * (quirks Q4 and Q9).  In RAFT_MODE_TEXTBOOK COMMITTED is final.
+ * Ordering as the drain's; the _dev form takes DEVICE pointers (ticket and
+ * out 16-byte aligned) and returns after its kernel finished. */
+#define RAFT_TICKET_NONE      0  /* the ticket stored nothing (NO_LEADER, LOG_FULL) */
+#define RAFT_TICKET_COMMITTED 1
+#define RAFT_TICKET_PENDING   2
+#define RAFT_TICKET_LOST      3
+#define RAFT_TICKET_UNKNOWN   4  /* log_window only: the answer depends on a slot below a window */
+#define RAFT_TICKET_INVALID   5  /* group, replica or index outside the engine: nothing was read */
+typedef struct raft_ticket_state {  /* 16 bytes */
+    int32_t status;
+    int32_t holders;       /* replicas r with index < lastIndex_r and log_r[index] == (term, cmd) */
+    int32_t committed_on;  /* holders with index < clamp(min(commitIndex_r, lastIndex_r), 0, log_cap) */
+    int32_t unknown;       /* replicas whose slot `index` is below their window (index < physLen_r - W) */
+} raft_ticket_state;
+int raft_engine_resolve_tickets    (raft_engine* e, const int64_t* group, const raft_ticket* ticket, const uint32_t* cmd,
+                                    raft_ticket_state* out, int64_t n);
+int raft_engine_resolve_tickets_dev(raft_engine* e, const int64_t* group, const raft_ticket* ticket, const uint32_t* cmd,
+                                    raft_ticket_state* out, int64_t n);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

@@ -189,6 +189,29 @@ APPLIED_DTYPE = np.dtype([("group", np.int64), ("replica", np.int32), ("index", 
                           ("cmd", np.uint32)])
 
 
+class raft_leader_info(C.Structure):
+    _fields_ = [("leader", C.c_int32), ("term", C.c_int32), ("n_leaders", C.c_int32), ("commit", C.c_int32)]
+
+
+class raft_ticket(C.Structure):
+    _fields_ = [("replica", C.c_int32), ("index", C.c_int32), ("term", C.c_int32), ("status", C.c_int32)]
+
+
+class raft_ticket_state(C.Structure):
+    _fields_ = [("status", C.c_int32), ("holders", C.c_int32), ("committed_on", C.c_int32), ("unknown", C.c_int32)]
+
+
+# the client path's records as numpy records (16 bytes each, no padding)
+LEADER_DTYPE = np.dtype([("leader", np.int32), ("term", np.int32), ("n_leaders", np.int32), ("commit", np.int32)])
+TICKET_DTYPE = np.dtype([("replica", np.int32), ("index", np.int32), ("term", np.int32), ("status", np.int32)])
+TICKET_STATE_DTYPE = np.dtype([("status", np.int32), ("holders", np.int32), ("committed_on", np.int32),
+                               ("unknown", np.int32)])
+# raft_ticket.status (RAFT_PROPOSE_*) and raft_ticket_state.status (RAFT_TICKET_*)
+PROPOSE_ACCEPTED, PROPOSE_GHOSTED, PROPOSE_NO_LEADER, PROPOSE_LOG_FULL = 0, 1, 2, 3
+TICKET_NONE, TICKET_COMMITTED, TICKET_PENDING, TICKET_LOST, TICKET_UNKNOWN, TICKET_INVALID = 0, 1, 2, 3, 4, 5
+TICKET_STATUS_NAMES = ["NONE", "COMMITTED", "PENDING", "LOST", "UNKNOWN", "INVALID"]
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -331,6 +354,11 @@ def load_library(path: str | None = None):
         "raft_engine_drain_committed_dev": (C.c_int, [eng, I64, I64, I32, C.c_void_p, I64, P(raft_drain_info)]),
         "raft_engine_read_applied": (C.c_int, [eng, I64, I64, P(I32)]),
         "raft_engine_write_applied": (C.c_int, [eng, I64, I64, P(I32)]),
+        "raft_engine_read_leaders": (C.c_int, [eng, I64, I64, C.c_void_p]),
+        "raft_propose_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_propose_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_resolve_tickets": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_resolve_tickets_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -383,6 +411,8 @@ EXPORTED_SYMBOLS = [
     "raft_engine_read_state", "raft_engine_write_state", "raft_engine_read_log",
     "raft_engine_write_log", "raft_engine_digest", "raft_engine_digest_range", "raft_engine_check_log_matching", "raft_engine_traffic_probe",
     "raft_engine_drain_committed", "raft_engine_drain_committed_dev", "raft_engine_read_applied", "raft_engine_write_applied",
+    "raft_engine_read_leaders", "raft_propose_batch", "raft_propose_batch_dev", "raft_engine_resolve_tickets",
+    "raft_engine_resolve_tickets_dev",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

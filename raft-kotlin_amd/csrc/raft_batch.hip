@@ -41,50 +41,7 @@ int grow_host(raft_engine* e, char** buf, size_t* have, size_t need) { return ra
 // single-handler batches: one lane per distinct (group, replica), its
 // messages applied in batch order
 // ---------------------------------------------------------------------------
-struct RepState {
-    int32_t term, voted, role, commit, last, phys, elec, phase, retry;
-    uint32_t fl;
-    int32_t t1, t2;
-    uint32_t c1;
-    __device__ Rep ref() { return Rep{term, voted, role, commit, last, phys, elec, phase, retry, fl, t1, t2, c1}; }
-};
-
-// The replica's state quads a handler needs (raft_step.h FIELD_SLOT), one
-// 16-B access and one 32-B sector each: quad 0 (term, votedFor, state, flags)
-// and quad 1 (lastIndex, physLen, t1, electionMs) for vote() and the timer
-// re-arm (RaftServer.kt:228-251); quad 2 (commitIndex, t2, c1, phaseMs) too
-// for append() and appendCommand (:253-287, :100-107).  Quad 3 (retryMs and
-// the primary session) no handler touches.  The log-tail cache (t1, t2, c1)
-// is the HBM copy: the batch path keeps it valid (run_batch_dev rebuilds it
-// first when a host write left it stale, and every run stores it back), so
-// vote() reads no log slot at all.
-struct RepQuads {
-    int4 q0, q1, q2;
-};
-template <bool VOTE_ONLY = false>
-__device__ __forceinline__ void load_rep(RepState& x, RepQuads& o, const DevParams& p, int64_t idx) {
-    o.q0 = *quad(p, 0, idx);
-    o.q1 = *quad(p, 1, idx);
-    o.q2 = VOTE_ONLY ? make_int4(0, 0, 0, 0) : *quad(p, 2, idx);
-    x.term = o.q0.x; x.voted = o.q0.y; x.role = o.q0.z; x.fl = (uint32_t)o.q0.w;
-    x.last = o.q1.x; x.phys = o.q1.y; x.t1 = o.q1.z; x.elec = o.q1.w;
-    x.commit = o.q2.x; x.t2 = o.q2.y; x.c1 = (uint32_t)o.q2.z; x.phase = o.q2.w;
-    x.retry = 0;                                                        // (quad 3: no handler touches it)
-}
-
-// Only the quads that changed are written back, whole (the run's thread owns
-// the replica): a random replica's quad is a 32-B sector of its own.
-template <bool VOTE_ONLY = false>
-__device__ __forceinline__ void store_rep(const RepState& x, const RepQuads& o, const DevParams& p, int64_t idx) {
-    const int4 q0 = make_int4(x.term, x.voted, x.role, (int32_t)(x.fl & FL_EXPORT_MASK));
-    const int4 q1 = make_int4(x.last, x.phys, x.t1, x.elec);
-    const int4 q2 = make_int4(x.commit, x.t2, (int32_t)x.c1, x.phase);
-    auto differ = [](int4 a, int4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; };
-    if (differ(q0, o.q0)) *quad(p, 0, idx) = q0;
-    if (differ(q1, o.q1)) *quad(p, 1, idx) = q1;
-    if (!VOTE_ONLY && differ(q2, o.q2)) *quad(p, 2, idx) = q2;
-}
-
+// (RepState, RepQuads, load_rep, store_rep: raft_engine_impl.h, shared with raft_client.hip)
 __device__ __forceinline__ bool resolve_rep_draw(RepState& x, const DevParams& p, uint32_t t, uint32_t gid, int r) {
     if (x.fl & FL_DRAW) {
         const u32x4 w = draw(p, t, gid, RAFT_RNG_TIMER, (uint32_t)(r >> 2));
@@ -97,15 +54,7 @@ __device__ __forceinline__ bool resolve_rep_draw(RepState& x, const DevParams& p
 
 enum { BATCH_VOTE = 0, BATCH_APPEND = 1, BATCH_COMMAND = 2 };
 
-// The batch handlers report one thing: reference accesses below the window
-// (the run is then invalid, RAFT_EWINDOW).  Called in divergent control flow:
-// a mask's bit for this lane is read with ib().
-struct BatchCounters {
-    uint32_t miss = 0;
-    __device__ __forceinline__ void add(uint64_t m, int c) {
-        if (c == RAFT_C_LOG_WINDOW_MISS) miss += ib(m) ? 1u : 0u;
-    }
-};
+// (BatchCounters: raft_engine_impl.h)
 
 // The batch path on the device (raft_*_batch, raft_*_batch_dev).  Messages
 // to one (group, replica) must be applied in batch order, and messages to

@@ -1212,6 +1212,8 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     e->applied_bytes = e->apl_bytes = e->apo_bytes = 0;
     for (hipEvent_t& x : e->ev_drain) x = nullptr;
     e->drain_timing = e->drain_expanded = false;
+    e->cli = e->cio = nullptr;
+    e->cli_bytes = e->cio_bytes = 0;
     e->hpart = nullptr;
     e->hpart_bytes = 0;
     e->device = device;
@@ -1392,6 +1394,8 @@ int raft_engine_destroy(raft_engine* e) {
     if (e->applied) (void)hipFree(e->applied);
     if (e->apl) (void)hipFree(e->apl);
     if (e->apo) (void)hipFree(e->apo);
+    if (e->cli) (void)hipFree(e->cli);
+    if (e->cio) (void)hipFree(e->cio);
     for (hipEvent_t x : e->ev_drain)
         if (x) (void)hipEventDestroy(x);
     if (e->hpart) (void)hipFree(e->hpart);
@@ -1687,7 +1691,7 @@ int raft_engine_set_step_index(raft_engine* e, int64_t t) {
 }
 int64_t raft_engine_device_bytes(raft_engine* e) {
     return e ? (int64_t)(e->bytes + e->bst_bytes + e->bio_bytes + e->aux_bytes + e->hpart_bytes + e->applied_bytes +
-                         e->apl_bytes + e->apo_bytes)
+                         e->apl_bytes + e->apo_bytes + e->cli_bytes + e->cio_bytes)
              : -1;
 }
 int raft_engine_trim_staging(raft_engine* e) {
@@ -1700,8 +1704,11 @@ int raft_engine_trim_staging(raft_engine* e) {
     if (e->hst) HIP_TRY(hipHostFree(e->hst));
     if (e->apl) HIP_TRY(hipFree(e->apl));
     if (e->apo) HIP_TRY(hipFree(e->apo));
-    e->bst = e->bio = e->aux = e->hst = e->apl = e->apo = nullptr;
+    if (e->cli) HIP_TRY(hipFree(e->cli));
+    if (e->cio) HIP_TRY(hipFree(e->cio));
+    e->bst = e->bio = e->aux = e->hst = e->apl = e->apo = e->cli = e->cio = nullptr;
     e->bst_bytes = e->bio_bytes = e->aux_bytes = e->hst_bytes = e->apl_bytes = e->apo_bytes = 0;
+    e->cli_bytes = e->cio_bytes = 0;
     return RAFT_OK;
 }
 

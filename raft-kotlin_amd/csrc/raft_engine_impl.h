@@ -1,8 +1,9 @@
 // raft_engine_impl.h — internal to the engine library: what raft_engine.hip
 // (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
-// batches, include/raft_engine.h raft_*_batch*) and raft_apply.hip (the
-// committed-entry drain) share -- the engine object, the
-// HBM indexing helpers and the error / staging entry points.  Not installed.
+// batches, include/raft_engine.h raft_*_batch*), raft_apply.hip (the
+// committed-entry drain) and raft_client.hip (the leader directory, routed
+// proposals and tickets) share -- the engine object, the HBM indexing helpers,
+// a replica's quad load / store and the error / staging entry points.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,6 +50,62 @@ __device__ __forceinline__ LogView log_of(const DevParams& p, int64_t idx) {
     const int lane = (int)(g - w * gpw) * p.R + (int)(idx - g * p.R);
     return LogView{p.log + (w * 64 + lane) * (int64_t)p.nslots, (uint32_t)p.nslots, p.wmask, p.cap, p.W};
 }
+
+// ---- one replica in registers: the handler batches (raft_batch.hip) and the
+// routed proposals (raft_client.hip) load, change and store it the same way
+struct RepState {
+    int32_t term, voted, role, commit, last, phys, elec, phase, retry;
+    uint32_t fl;
+    int32_t t1, t2;
+    uint32_t c1;
+    __device__ Rep ref() { return Rep{term, voted, role, commit, last, phys, elec, phase, retry, fl, t1, t2, c1}; }
+};
+
+// The replica's state quads a handler needs (raft_step.h FIELD_SLOT), one
+// 16-B access and one 32-B sector each: quad 0 (term, votedFor, state, flags)
+// and quad 1 (lastIndex, physLen, t1, electionMs) for vote() and the timer
+// re-arm (RaftServer.kt:228-251); quad 2 (commitIndex, t2, c1, phaseMs) too
+// for append() and appendCommand (:253-287, :100-107).  Quad 3 (retryMs and
+// the primary session) no handler touches.  The log-tail cache (t1, t2, c1)
+// is the HBM copy: the batch path keeps it valid (run_batch_dev rebuilds it
+// first when a host write left it stale, and every run stores it back), so
+// vote() reads no log slot at all.
+struct RepQuads {
+    int4 q0, q1, q2;
+};
+template <bool VOTE_ONLY = false>
+__device__ __forceinline__ void load_rep(RepState& x, RepQuads& o, const DevParams& p, int64_t idx) {
+    o.q0 = *quad(p, 0, idx);
+    o.q1 = *quad(p, 1, idx);
+    o.q2 = VOTE_ONLY ? make_int4(0, 0, 0, 0) : *quad(p, 2, idx);
+    x.term = o.q0.x; x.voted = o.q0.y; x.role = o.q0.z; x.fl = (uint32_t)o.q0.w;
+    x.last = o.q1.x; x.phys = o.q1.y; x.t1 = o.q1.z; x.elec = o.q1.w;
+    x.commit = o.q2.x; x.t2 = o.q2.y; x.c1 = (uint32_t)o.q2.z; x.phase = o.q2.w;
+    x.retry = 0;                                                        // (quad 3: no handler touches it)
+}
+
+// Only the quads that changed are written back, whole (the run's thread owns
+// the replica): a random replica's quad is a 32-B sector of its own.
+template <bool VOTE_ONLY = false>
+__device__ __forceinline__ void store_rep(const RepState& x, const RepQuads& o, const DevParams& p, int64_t idx) {
+    const int4 q0 = make_int4(x.term, x.voted, x.role, (int32_t)(x.fl & FL_EXPORT_MASK));
+    const int4 q1 = make_int4(x.last, x.phys, x.t1, x.elec);
+    const int4 q2 = make_int4(x.commit, x.t2, (int32_t)x.c1, x.phase);
+    auto differ = [](int4 a, int4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; };
+    if (differ(q0, o.q0)) *quad(p, 0, idx) = q0;
+    if (differ(q1, o.q1)) *quad(p, 1, idx) = q1;
+    if (!VOTE_ONLY && differ(q2, o.q2)) *quad(p, 2, idx) = q2;
+}
+
+// The batch handlers report one thing: reference accesses below the window
+// (the run is then invalid, RAFT_EWINDOW).  Called in divergent control flow:
+// a mask's bit for this lane is read with ib().
+struct BatchCounters {
+    uint32_t miss = 0;
+    __device__ __forceinline__ void add(uint64_t m, int c) {
+        if (c == RAFT_C_LOG_WINDOW_MISS) miss += ib(m) ? 1u : 0u;
+    }
+};
 }  // namespace
 
 struct raft_engine {
@@ -111,6 +168,12 @@ struct raft_engine {
     size_t apo_bytes;
     hipEvent_t ev_drain[5];     // pass boundaries of the last drain while drain_timing (scripts/drain_probe.py)
     bool drain_timing, drain_expanded;
+    // the client path (raft_client.hip), grow-only: device scratch (keys, sort, status words) and the device
+    // copies of a host call's arrays; host calls stage through hst like the batches
+    char* cli;
+    size_t cli_bytes;
+    char* cio;
+    size_t cio_bytes;
     int64_t* counters_dev;      // [K][STRIDE] scratch
     unsigned long long* accum;  // [K * NC] counter accumulators: sum + chunks done << 48 (zero between launches)
     // step-kernel event timing

@@ -325,6 +325,88 @@ class RaftEngine:
         a = np.ascontiguousarray(a, dtype=np.int32)
         self._check(self._lib.raft_engine_write_applied(self._h, g0, a.shape[0], abi.ptr(a, C.c_int32)), "write_applied")
 
+    # -- the client path: leader directory, routed proposals, tickets ---------
+    def leaders(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """The leader directory of groups [g0, g0 + n): abi.LEADER_DTYPE records
+        (leader: the lowest replica index with role LEADER or -1, its term and
+        commitIndex, n_leaders) -- 16 bytes per group, no whole-state copy."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros(max(int(n), 0), dtype=abi.LEADER_DTYPE)       # a bad range is the library's to refuse
+        self._check(self._lib.raft_engine_read_leaders(self._h, int(g0), int(n), C.c_void_p(out.ctypes.data)),
+                    "read_leaders")
+        return out
+
+    @staticmethod
+    def _client_arrays(groups, cmds, what: str):
+        """groups / cmds as contiguous int64 / uint32 vectors of one length
+        (the C side reads n of each)."""
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        c = np.ascontiguousarray(cmds, dtype=np.uint32)
+        if g.ndim != 1 or c.ndim != 1 or g.shape[0] != c.shape[0]:
+            raise ValueError(f"{what}: groups {g.shape} and cmds {c.shape} must be 1-D and of one length")
+        return g, c
+
+    def _client_status(self, rc: int, what: str, allowed=(abi.RAFT_EWINDOW,)) -> int:
+        """Raise on an error the call did not survive; a code in `allowed` (the
+        call did everything else) is kept in ``last_status`` instead."""
+        if rc not in allowed:
+            self._check(rc, what)
+        self.last_status = int(rc)
+        return int(rc)
+
+    def propose(self, groups, cmds) -> np.ndarray:
+        """raft_propose_batch: command cmds[m] (a u32 id) to the leader of
+        groups[m], in batch order; returns abi.TICKET_DTYPE tickets (replica,
+        index, term, status = abi.PROPOSE_*).  RAFT_EWINDOW (a textbook add
+        below a log_window) is not raised: the batch was applied, the tickets
+        are returned and ``last_status`` carries the code."""
+        g, c = self._client_arrays(groups, cmds, "propose")
+        t = np.zeros(g.shape[0], dtype=abi.TICKET_DTYPE)
+        self._client_status(self._lib.raft_propose_batch(self._h, C.c_void_p(g.ctypes.data), C.c_void_p(c.ctypes.data),
+                                                         C.c_void_p(t.ctypes.data), g.shape[0]), "raft_propose_batch")
+        return t
+
+    def propose_dev(self, group_ptr: int, cmd_ptr: int, ticket_ptr: int, n: int,
+                    after_stream: int | None = None) -> int:
+        """raft_propose_batch_dev: DEVICE pointers to n int64 groups, uint32
+        commands and 16-byte tickets (16-byte aligned); returns RAFT_OK or
+        RAFT_EWINDOW once the batch finished."""
+        if ticket_ptr % 16:
+            raise ValueError("propose_dev: the ticket buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_propose_batch_dev(self._h, group_ptr, cmd_ptr, ticket_ptr, int(n)),
+                                   "raft_propose_batch_dev")
+
+    def resolve(self, groups, tickets, cmds, check: bool = True) -> np.ndarray:
+        """raft_engine_resolve_tickets: what became of each ticket's entry, as
+        abi.TICKET_STATE_DTYPE records (status = abi.TICKET_*, holders,
+        committed_on, unknown).  Read-only.  RAFT_EWINDOW (some record is
+        UNKNOWN) is never raised; with check=False neither are RAFT_ERANGE /
+        RAFT_EINVAL (some record is INVALID): ``last_status`` carries the code."""
+        g, c = self._client_arrays(groups, cmds, "resolve")
+        t = np.ascontiguousarray(tickets)
+        if t.dtype != abi.TICKET_DTYPE or t.ndim != 1 or t.shape[0] != g.shape[0]:
+            raise ValueError(f"resolve: tickets must be {g.shape[0]} records of abi.TICKET_DTYPE")
+        out = np.zeros(g.shape[0], dtype=abi.TICKET_STATE_DTYPE)
+        allowed = (abi.RAFT_EWINDOW,) if check else (abi.RAFT_EWINDOW, abi.RAFT_ERANGE, abi.RAFT_EINVAL)
+        self._client_status(self._lib.raft_engine_resolve_tickets(
+            self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(c.ctypes.data),
+            C.c_void_p(out.ctypes.data), g.shape[0]), "raft_engine_resolve_tickets", allowed)
+        return out
+
+    def resolve_dev(self, group_ptr: int, ticket_ptr: int, cmd_ptr: int, out_ptr: int, n: int,
+                    after_stream: int | None = None) -> int:
+        """raft_engine_resolve_tickets_dev on DEVICE pointers (tickets and
+        records 16-byte aligned); returns RAFT_OK or RAFT_EWINDOW."""
+        if ticket_ptr % 16 or out_ptr % 16:
+            raise ValueError("resolve_dev: the ticket and record buffers must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_engine_resolve_tickets_dev(self._h, group_ptr, ticket_ptr, cmd_ptr,
+                                                                             out_ptr, int(n)),
+                                   "raft_engine_resolve_tickets_dev")
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

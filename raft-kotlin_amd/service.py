@@ -15,6 +15,9 @@ argument meaning and error behaviour:
   (RaftServer.kt:96-97)
 * ``lastApplied`` (RaftServer.kt:47) and ``RaftService.poll_committed``: the
   entries that became committed since the last poll, for a state machine to apply
+* ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
+  reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
+  leader, a command routed to it with a ticket, and that ticket's fate
 
 Commands are strings in the reference (LogEntry.command, greeter.proto:31); the
 engine stores a u32 id per entry, interned here.  Every call is one HIP batch;
@@ -194,6 +197,27 @@ class RaftService:
         return ((g, r, i, t, name(c)) for g, r, i, t, c in
                 zip(rec["group"].tolist(), rec["replica"].tolist(), rec["index"].tolist(), rec["term"].tolist(),
                     rec["cmd"].tolist()))
+
+    # -- the client path: /cmd/{command} (RaftServer.kt:87-88) with an answer ---
+    def leader(self, group: int) -> Optional[RaftNode]:
+        """The group's leader node (the lowest id when there are several), or
+        None: one 16-byte read, not RaftNode.state on every replica."""
+        r = int(self.engine.leaders(group, 1)["leader"][0])
+        return None if r < 0 else RaftNode(self, group, r)
+
+    def submit(self, groups, commands: List[str]) -> np.ndarray:
+        """One command per entry of `groups`, routed to each group's leader in
+        the order given; returns the tickets (abi.TICKET_DTYPE).  A ticket with
+        status abi.PROPOSE_NO_LEADER or PROPOSE_LOG_FULL stored nothing: the
+        client retries it later."""
+        return self.engine.propose(groups, [self.commands.intern(c) for c in commands])
+
+    def status(self, groups, tickets, commands: List[str]) -> List[str]:
+        """What became of each submitted command: "COMMITTED", "PENDING", "LOST",
+        "NONE" (nothing was stored), "UNKNOWN" (log_window: the slot left a
+        window).  ``last_status`` keeps the records (holders, committed_on, unknown)."""
+        self.last_status = self.engine.resolve(groups, tickets, [self.commands.intern(c) for c in commands])
+        return [abi.TICKET_STATUS_NAMES[s] for s in self.last_status["status"].tolist()]
 
     # -- the gRPC-facing wire form (include/raft_wire.h) --------------------
     # RaftImplBase.vote()/append() (RaftServer.kt:228, :253) receive and return

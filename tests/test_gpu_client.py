@@ -1,0 +1,260 @@
+"""The client path on the GPU (marker `gpu`): raft_engine_read_leaders,
+raft_propose_batch* and raft_engine_resolve_tickets* against the plain-Python
+model of tests/client_model.py over the oracle.  Every comparison is exact."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import client_model as M
+import oracle as O
+from helpers import abi, assert_same_logs, assert_same_state
+
+pytestmark = pytest.mark.gpu
+
+eng_mod = importlib.import_module("raft-kotlin_amd.engine")
+RaftEngine = eng_mod.RaftEngine
+RaftError = eng_mod.RaftError
+NC = abi.NUM_COUNTERS
+
+
+def same(got, want, label=""):
+    assert got.dtype == want.dtype and len(got) == len(want), (label, got.dtype, len(got), len(want))
+    if not np.array_equal(got, want):
+        at = int(np.nonzero(got != want)[0][0])
+        raise AssertionError(f"{label}: {int((got != want).sum())} records differ; first at {at}: {got[at]} vs {want[at]}")
+
+
+@pytest.mark.parametrize("textbook", [False, True], ids=["reference", "textbook"])
+def test_crafted_state(textbook):
+    """No leader, one leader, two leaders (the lowest id wins), a leader at
+    R - 1, a ghost tail (GHOSTED / ACCEPTED), a full log (LOG_FULL), and three
+    proposals to one group interleaved among the others."""
+    R, G, cap = 3, 8, 16
+    o, kw = M.crafted_oracle(textbook)
+    w, t, c = M.crafted(R, G, cap)
+    with RaftEngine(abi.make_params(**kw)) as e:
+        e.write_state(w)
+        e.write_log(t, c)
+        same(e.leaders(), M.leaders(w, R), "leaders")
+        same(e.leaders(2, 3), M.leaders(w, R)[2:5], "leaders of a slice")
+        want, wrc = M.propose(o, M.CRAFTED_GROUPS, M.CRAFTED_CMDS, textbook)
+        got = e.propose(M.CRAFTED_GROUPS, M.CRAFTED_CMDS)
+        same(got, want, "tickets")
+        assert e.last_status == wrc == abi.RAFT_OK
+        assert got["index"][M.CRAFTED_GROUPS == 1].tolist() == [5, 6, 7]
+        assert got["status"][5] == (M.ACCEPTED if textbook else M.GHOSTED) and got["status"][6] == M.LOG_FULL
+        st = o.read_state()
+        assert_same_state(e.read_state(), st, R, "state after the batch")
+        assert_same_logs(st, e.read_log(), o.read_log(), R, "logs after the batch")
+        assert e.digest() == o.digest()
+        same(e.leaders(), M.leaders(st, R), "leaders after the batch")           # appendCommand changes no role
+        wrec, wrc = M.resolve(st, *o.read_log(), M.CRAFTED_GROUPS, want, M.CRAFTED_CMDS, R, cap)
+        same(e.resolve(M.CRAFTED_GROUPS, got, M.CRAFTED_CMDS), wrec, "records")
+        assert e.last_status == wrc == abi.RAFT_OK
+        old = np.array([(1, 1, int(t[6, 1, 1]), M.ACCEPTED)] * 2, dtype=abi.TICKET_DTYPE)
+        rec = e.resolve([6, 6], old, [int(c[6, 1, 1]), 5])
+        assert rec.tolist() == [(M.COMMITTED, 3, 3, 0), (M.LOST, 0, 0, 0)]
+        assert e.digest() == o.digest() and not e.applied().any()               # resolve is read-only
+    o.close()
+
+
+def lockstep_case(R, textbook, W):
+    kw = dict(R=R, G=203, seed=11, log_cap=300)
+    if textbook:
+        kw.update(mode=1, ae_max_entries=4)
+    if W:
+        kw.update(log_window=W, **M.RING_MIX)
+    else:
+        kw.update(M.FLAT_MIX)
+    # 200 steps; the reference's log in a 16-slot ring keeps up with these batches for 50 steps only (its ghost
+    # tail, Q1, outgrows the window: the oracle's RAFT_C_LOG_WINDOW_MISS rows say so), and an invalid run is
+    # not comparable: that case stops after 45
+    return kw, (45 if W and not textbook else 200)
+
+
+@pytest.mark.parametrize("W", [0, 16], ids=["flat", "ring16"])
+@pytest.mark.parametrize("textbook", [False, True], ids=["reference", "textbook"])
+@pytest.mark.parametrize("R", [1, 3, 5, 8])
+def test_lockstep_against_the_oracle(R, textbook, W):
+    """A batch every 5 steps (1, 63, 64, 65, 700 messages, the 700 with a hot
+    group's burst): tickets, the resolve records of every ticket so far, the
+    digest, and the next 5 steps' counter rows -- the step kernel reading the
+    log-tail cache the batch left -- all equal the oracle's."""
+    kw, steps = lockstep_case(R, textbook, W)
+    every = 5
+    batches, counters, (ag, at, ac), (st, lt, lc, digest) = M.oracle_run(steps, every, **kw)
+    label = f"R{R} tb{int(textbook)} W{W}"
+    with RaftEngine(abi.make_params(**kw)) as e:
+        for k, b in enumerate(batches):
+            rows = e.step(every)
+            assert np.array_equal(rows, counters[k * every:(k + 1) * every, :NC]), f"{label}: counter rows before batch {k}"
+            same(e.leaders(), b["leaders"], f"{label} leaders {k}")
+            got = e.propose(b["groups"], b["cmds"])
+            same(got, b["tickets"], f"{label} tickets {k}")
+            assert e.last_status == b["propose_rc"], (label, k)
+            n = len(b["records"])
+            same(e.resolve(ag[:n], at[:n], ac[:n]), b["records"], f"{label} records {k}")
+            assert e.last_status == b["resolve_rc"], (label, k)
+            assert e.digest() == b["digest"], f"{label}: digest after batch {k}"
+        rows = e.step(every)
+        assert np.array_equal(rows, counters[steps:, :NC]), f"{label}: counter rows after the last batch"
+        got_state = e.read_state()
+        assert_same_state(got_state, st, R, label)
+        assert_same_logs(st, e.read_log(), (lt, lc), R, label)
+        assert e.digest() == digest and not e.applied().any()
+    # the run was worth comparing: proposals were stored, some committed
+    h = M.history(batches)
+    assert (at["status"] == M.ACCEPTED).any() and (h == M.COMMITTED).any(), label
+    if steps == 200:
+        assert (at["status"] == M.NO_LEADER).any(), label
+
+
+def test_vote_batch_reads_the_cache_a_propose_left():
+    """propose, then vote_batch on the same replicas: vote() answers from the
+    HBM log-tail cache (no log read), which the propose kernel stored."""
+    kw = dict(R=5, G=203, seed=11, log_cap=300, **M.FLAT_MIX)
+    o = O.Oracle(abi.make_params(**kw))
+    rng = np.random.default_rng(3)
+    with RaftEngine(abi.make_params(**kw)) as e:
+        e.step(60, counters=False)
+        o.step(60, counters=False)
+        groups, cmds = M.batch_of(rng, 700, 203, 0, 0)
+        want, _ = M.propose(o, groups, cmds)
+        got = e.propose(groups, cmds)
+        same(got, want, "tickets")
+        led = got["replica"] >= 0
+        assert led.sum() > 300
+        g, d, tk = groups[led], got["replica"][led], got[led]
+        # candidates of a later term whose log is just behind, level with or ahead of the entry just stored
+        req = np.stack([tk["term"] + 1 + rng.integers(0, 2, len(g)), (d + 1) % 5 + 1,
+                        tk["index"] + rng.integers(0, 3, len(g)), tk["term"] - rng.integers(0, 2, len(g))], axis=1)
+        resp = e.vote_batch(g, d, req.astype(np.int32))
+        wresp = np.array([o.vote(int(a), int(b), *map(int, q)) for a, b, q in zip(g, d, req)], dtype=np.int32)
+        assert np.array_equal(resp, wresp)
+        assert 0 < resp[:, 1].sum() < len(resp)
+        assert_same_state(e.read_state(), o.read_state(), 5, "after the votes")
+        assert e.digest() == o.digest()
+    o.close()
+
+
+def test_dev_variants_equal_host_variants():
+    import torch
+    kw = dict(R=5, G=203, seed=11, log_cap=300, **M.FLAT_MIX)
+    rng = np.random.default_rng(4)
+    groups, cmds = M.batch_of(rng, 700, 203, 0, 0)
+    with RaftEngine(abi.make_params(**kw)) as a, RaftEngine(abi.make_params(**kw)) as b:
+        a.step(60, counters=False)
+        b.step(60, counters=False)
+        host = a.propose(groups, cmds)
+        dg = torch.from_numpy(groups).to("cuda:0")
+        dc = torch.from_numpy(cmds.view(np.int32)).to("cuda:0")
+        dt = torch.zeros((len(groups) + 1) * 4, dtype=torch.int32, device="cuda:0")
+        dr = torch.zeros((len(groups) + 1) * 4, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        assert b.propose_dev(dg.data_ptr(), dc.data_ptr(), dt.data_ptr(), len(groups)) == abi.RAFT_OK
+        raw = dt.cpu().numpy()
+        same(raw[:-4].view(abi.TICKET_DTYPE), host, "device tickets")
+        assert not raw[-4:].any()                              # nothing written beyond the tickets
+        assert a.digest() == b.digest()
+        a.step(10, counters=False)
+        b.step(10, counters=False)
+        want = a.resolve(groups, host, cmds)
+        assert b.resolve_dev(dg.data_ptr(), dt.data_ptr(), dc.data_ptr(), dr.data_ptr(), len(groups)) == abi.RAFT_OK
+        raw = dr.cpu().numpy()
+        same(raw[:-4].view(abi.TICKET_STATE_DTYPE), want, "device records")
+        assert not raw[-4:].any() and (want["status"] == M.COMMITTED).any()
+        assert a.digest() == b.digest()
+
+
+def test_arguments():
+    R, G, cap = 3, 8, 16
+    w, t, c = M.crafted(R, G, cap)
+    lib = abi.load_library()
+    p = lambda x: C.c_void_p(x.ctypes.data)
+    with RaftEngine(abi.make_params(R=R, G=G, log_cap=cap)) as e:
+        e.write_state(w)
+        e.write_log(t, c)
+        d0 = e.digest()
+        # a bad group fails the whole batch before anything is applied
+        for bad in (G, -1, 1 << 40):
+            with pytest.raises(RaftError, match="outside"):
+                e.propose([1, bad, 2], [5, 6, 7])
+            assert e.digest() == d0
+        for g0, n in ((0, G + 1), (G, 1), (-1, 2), (3, -1)):
+            with pytest.raises(RaftError, match="range"):
+                e.leaders(g0, n)
+        # n = 0 and null pointers
+        assert len(e.propose([], [])) == 0 and len(e.resolve([], np.zeros(0, abi.TICKET_DTYPE), [])) == 0
+        assert len(e.leaders(3, 0)) == 0
+        g2, c2 = np.array([1, 2], np.int64), np.array([5, 6], np.uint32)
+        t2, s2 = np.zeros(2, abi.TICKET_DTYPE), np.zeros(2, abi.TICKET_STATE_DTYPE)
+        assert lib.raft_propose_batch(e._h, None, None, None, 0) == abi.RAFT_OK
+        assert lib.raft_engine_resolve_tickets(e._h, None, None, None, None, 0) == abi.RAFT_OK
+        for args in ((None, p(c2), p(t2)), (p(g2), None, p(t2)), (p(g2), p(c2), None)):
+            assert lib.raft_propose_batch(e._h, *args, 2) == abi.RAFT_EINVAL
+            assert lib.raft_propose_batch_dev(e._h, *args, 2) == abi.RAFT_EINVAL
+        assert lib.raft_propose_batch(e._h, p(g2), p(c2), p(t2), -1) == abi.RAFT_EINVAL
+        assert lib.raft_propose_batch(e._h, p(g2), p(c2), p(t2), 1 << 31) == abi.RAFT_EINVAL
+        assert lib.raft_engine_resolve_tickets(e._h, p(g2), p(t2), p(c2), None, 2) == abi.RAFT_EINVAL
+        assert lib.raft_engine_read_leaders(e._h, 0, 2, None) == abi.RAFT_EINVAL
+        assert e.digest() == d0
+        # bad tickets: INVALID and the return code, the other records still filled
+        tk = e.propose([1, 1], [5, 6])
+        bad = np.array([tuple(tk[0]), (1, cap, 4, 0), (R, 5, 4, 0), (1, -1, 4, 0), tuple(tk[1])], dtype=abi.TICKET_DTYPE)
+        groups, cmds = [1, 1, 1, 1, 1], [5, 5, 5, 5, 6]
+        rec = e.resolve(groups, bad, cmds, check=False)
+        assert e.last_status == abi.RAFT_EINVAL
+        assert rec["status"].tolist() == [M.PENDING, M.INVALID, M.INVALID, M.INVALID, M.PENDING]
+        st, (lt, lc) = e.read_state(), e.read_log()
+        same(rec, M.resolve(st, lt, lc, groups, bad, cmds, R, cap)[0], "bad tickets")
+        with pytest.raises(RaftError, match="replica or index"):
+            e.resolve(groups, bad, cmds)
+        groups[3] = G                                          # and a bad group: RAFT_ERANGE goes first
+        rec = e.resolve(groups, bad, cmds, check=False)
+        assert e.last_status == abi.RAFT_ERANGE
+        same(rec, M.resolve(st, lt, lc, groups, bad, cmds, R, cap)[0], "bad group")
+        # a NO_LEADER ticket (replica -1, index -1) is NONE, not INVALID
+        none = e.propose([0], [9])
+        assert none.tolist() == [(-1, -1, 0, M.NO_LEADER)]
+        assert e.resolve([0], none, [9]).tolist() == [(M.NONE, 0, 0, 0)] and e.last_status == abi.RAFT_OK
+
+
+def test_staging_is_counted_and_trimmed():
+    kw = dict(R=3, G=300, seed=4, log_cap=64)
+    rng = np.random.default_rng(6)
+    with RaftEngine(abi.make_params(**kw)) as e:
+        idle = e.device_bytes
+        e.step(30, counters=False)
+        groups, cmds = rng.integers(0, 300, 5000, dtype=np.int64), rng.integers(1, 2 ** 32, 5000, dtype=np.uint32)
+        tk = e.propose(groups, cmds)
+        grown = e.device_bytes
+        assert grown > idle
+        rec = e.resolve(groups, tk, cmds)
+        e.leaders()
+        e.trim_staging()
+        assert e.device_bytes == idle
+        same(e.resolve(groups, tk, cmds), rec, "after the trim")
+        assert e.device_bytes > idle
+
+
+def test_service_submit_and_status():
+    svc_mod = importlib.import_module("raft-kotlin_amd.service")
+    R, G, cap = 3, 8, 16
+    w, t, c = M.crafted(R, G, cap)
+    with RaftEngine(abi.make_params(R=R, G=G, log_cap=cap)) as e:
+        e.write_state(w)
+        e.write_log(t, c)
+        svc = svc_mod.RaftService(e)
+        assert svc.leader(0) is None and svc.leader(2).replica == 0 and svc.leader(3).id == R
+        names = ["set x 1", "set y 2", "del x"]
+        tk = svc.submit([1, 0, 1], names)
+        assert tk["status"].tolist() == [M.ACCEPTED, M.NO_LEADER, M.ACCEPTED] and tk["index"].tolist() == [5, -1, 6]
+        assert svc.status([1, 0, 1], tk, names) == ["PENDING", "NONE", "PENDING"]
+        assert svc.leader(1).entries()[5:] == ["4: set x 1", "4: del x"]
+        s = e.read_state()
+        s[1, 1 * abi.NUM_FIELDS + abi.F_INDEX["commit"]] = 6
+        e.write_state(s)
+        assert svc.status([1, 0, 1], tk, names) == ["COMMITTED", "NONE", "PENDING"]
+        assert svc.status([1], tk[:1], ["another"]) == ["LOST"]
