@@ -44,8 +44,9 @@ extern "C" {
  * subranges by workload (1 or 3), raft_engine_kernel_info, raft_engine_set_kernel,
  * raft_engine_reset, raft_engine_wait_stream.  Added since without a new
  * version, because nothing that existed changed: committed-entry delivery
- * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied) and the
- * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*) */
+ * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied), the
+ * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*)
+ * and the replicated state machine (raft_engine_sm_*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -332,8 +333,8 @@ int     raft_engine_reset(raft_engine* e);
  * harness draws, `t % partition_period` and a partition window's first step
  * are all taken in uint32_t), and raft_engine_step_index reports it mod 2^32. */
 int     raft_engine_set_step_index(raft_engine* e, int64_t t);
-/* HBM owned by the engine: the state, logs, counter buffers and lastApplied,
- * plus the grow-only staging of the handler batches, accessors, drains and client path (kept for the
+/* HBM owned by the engine: the state, logs, counter buffers, lastApplied and a
+ * configured state machine, plus the grow-only staging of the handler batches, accessors, drains and client path (kept for the
  * engine's lifetime at 1.25x the largest request; raft_engine_trim_staging
  * frees it, page-locked host staging included). */
 /* ---- multi-GPU: the counter all-reduce ----------------
@@ -562,6 +563,96 @@ int raft_engine_resolve_tickets    (raft_engine* e, const int64_t* group, const 
                                     raft_ticket_state* out, int64_t n);
 int raft_engine_resolve_tickets_dev(raft_engine* e, const int64_t* group, const raft_ticket* ticket, const uint32_t* cmd,
                                     raft_ticket_state* out, int64_t n);
+
+/* ---- the replicated state machine: committed entries applied on the device --
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The step after "committed": a state machine per replica that consumes its
+ * replica's committed entries in log order, in HBM, with no record written
+ * per entry.  Opt-in: raft_engine_sm_configure(e, S) allocates it (S register
+ * slots, a power of two in 1..64), and until then every other
+ * raft_engine_sm_* call returns RAFT_EINVAL.  The canonical state, the
+ * digest, the step kernel and the drain's lastApplied do not know about it.
+ *
+ * Per replica: reg[S] uint32 (0), hash uint64 (0), applied int32 (0: the
+ * machine's own cursor, independent of the drain's lastApplied -- a caller may
+ * drain to the host and apply on the device side by side) and lost int32 (0;
+ * log_window only).  Applying entry (index i, term t, cmd c):
+ *   reg[c & (S - 1)] = c                                    last writer wins
+ *   hash = hash * 0xD1342543DE82EF95 + x(i, t, c)           mod 2^64
+ *   x    = fmix((((uint64)(uint32)t << 32) | c) + (uint64)(uint32)i * 0x9E3779B97F4A7C15)
+ *   fmix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ * Entries apply in ascending index.
+ *
+ * raft_engine_sm_apply visits the selected replicas of groups [g0, g0 + n) as
+ * the drain does (replica = -1: every replica; else that replica index of each
+ * group).  For each, with hi = clamp(min(commitIndex, lastIndex), 0, log_cap)
+ * and lo = applied:
+ * - with a log_window W and wl = max(0, physLen - W): if wl > lo and hi > lo,
+ *   the min(wl, hi) - lo entries below the window are gone; they are added to
+ *   the replica's `lost` and to info->lost, the cursor moves past them, and the
+ *   call returns RAFT_EWINDOW after doing everything else;
+ * - if hi < lo the replica is counted in info->regressed; nothing is applied
+ *   and its cursor is unchanged;
+ * - else entries lo .. hi - 1 are applied and applied = hi.
+ * There is no max_entries: nothing is written per entry.
+ *
+ * Not promised, as with the drain: in RAFT_MODE_REFERENCE an applied entry may
+ * later be overwritten in the log (quirks Q1-Q4, Q9); a replica's machine is
+ * then not the fold of its current log, and a group's replicas may diverge.
+ * In RAFT_MODE_TEXTBOOK with a flat log a replica's machine always equals the
+ * fold of log[0, applied).
+ *
+ * Ordering is the drain's: the call runs on the engine stream, sees every step
+ * enqueued before it, later step launches wait for it, and it returns when its
+ * kernel has finished. */
+typedef struct raft_sm_info {         /* 32 bytes */
+    int64_t applied;     /* entries applied by this call */
+    int64_t lost;        /* log_window only: entries that left the window unapplied; skipped */
+    int64_t regressed;   /* selected replicas whose min(commit, last) < applied */
+    int64_t reserved;    /* 0 */
+} raft_sm_info;
+typedef struct raft_sm_head {         /* 16 bytes */
+    int32_t  applied;    /* entries [0, applied) of the replica's log were consumed (or skipped: lost) */
+    int32_t  lost;       /* of those, the entries that were never applied */
+    uint64_t hash;
+} raft_sm_head;
+typedef struct raft_sm_value {        /* 16 bytes */
+    uint32_t value;      /* reg[key & (S - 1)] of the chosen replica, 0 if none */
+    int32_t  replica;    /* the replica read: the one asked for, or the group's leader; -1 if it has none */
+    int32_t  applied;    /* that replica's cursor ... */
+    int32_t  commit;     /* ... and its commitIndex: how stale the answer is (0 if none) */
+} raft_sm_value;
+/* Allocate and zero the machine with `slots` registers per replica (again: zero
+ * it, or reallocate for another count); slots = 0 frees it.  RAFT_EINVAL:
+ * null engine, slots not 0 or a power of two in 1..64.  The allocation counts
+ * in raft_engine_device_bytes, raft_engine_trim_staging keeps it, and
+ * raft_engine_reset zeroes it. */
+int raft_engine_sm_configure(raft_engine* e, int32_t slots);
+/* RAFT_EINVAL: null engine or info, not configured, replica outside -1..R-1;
+ * RAFT_ERANGE: groups outside the engine. */
+int raft_engine_sm_apply(raft_engine* e, int64_t g0, int64_t n, int32_t replica, raft_sm_info* info);
+/* The machines of groups [g0, g0 + n): heads [n][R], regs [n][R][S] (host;
+ * either may be NULL).  sm_write resumes a run (with write_state / write_log):
+ * every applied must be in 0..log_cap and every lost >= 0, else RAFT_EINVAL
+ * and nothing is stored. */
+int raft_engine_sm_read(raft_engine* e, int64_t g0, int64_t n, raft_sm_head* heads, uint32_t* regs);
+int raft_engine_sm_write(raft_engine* e, int64_t g0, int64_t n, const raft_sm_head* heads, const uint32_t* regs);
+/* The batched client read: out[m] = register key[m] of replica[m] of group[m]
+ * (host arrays of n); replica[m] = -1 reads the group's leader as
+ * raft_leader_info.leader chooses it.  A group outside the engine or a replica
+ * outside -1..R-1 fails the whole batch with RAFT_ERANGE (nothing is filled).
+ * n == 0 is RAFT_OK.  RAFT_EINVAL: null engine, not configured, n < 0 or
+ * n >= 2^31, a null buffer with n > 0. */
+int raft_engine_sm_get(raft_engine* e, const int64_t* group, const int32_t* replica, const uint32_t* key,
+                       raft_sm_value* out, int64_t n);
+/* State Machine Safety (the shape of raft_engine_check_log_matching): a group
+ * of [g0, g0 + n) is flagged when two of its replicas have lost == 0, equal
+ * applied and different hash.  *diverged = flagged groups; flags (nullable,
+ * host, n bytes) receives 1 per flagged group.  An observation about the
+ * protocol, never an engine error: RAFT_MODE_REFERENCE can flag groups
+ * (quirks Q4, Q9), RAFT_MODE_TEXTBOOK must not. */
+int raft_engine_sm_check(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, int64_t* diverged);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

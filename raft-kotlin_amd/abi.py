@@ -212,6 +212,24 @@ TICKET_NONE, TICKET_COMMITTED, TICKET_PENDING, TICKET_LOST, TICKET_UNKNOWN, TICK
 TICKET_STATUS_NAMES = ["NONE", "COMMITTED", "PENDING", "LOST", "UNKNOWN", "INVALID"]
 
 
+class raft_sm_info(C.Structure):
+    _fields_ = [("applied", C.c_int64), ("lost", C.c_int64), ("regressed", C.c_int64), ("reserved", C.c_int64)]
+
+
+class raft_sm_head(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("lost", C.c_int32), ("hash", C.c_uint64)]
+
+
+class raft_sm_value(C.Structure):
+    _fields_ = [("value", C.c_uint32), ("replica", C.c_int32), ("applied", C.c_int32), ("commit", C.c_int32)]
+
+
+# the state machine's records as numpy records (16 bytes each, no padding)
+SM_HEAD_DTYPE = np.dtype([("applied", np.int32), ("lost", np.int32), ("hash", np.uint64)])
+SM_VALUE_DTYPE = np.dtype([("value", np.uint32), ("replica", np.int32), ("applied", np.int32), ("commit", np.int32)])
+SM_SLOTS = (1, 2, 4, 8, 16, 32, 64)      # raft_engine_sm_configure: registers per replica
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -359,6 +377,12 @@ def load_library(path: str | None = None):
         "raft_propose_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_engine_resolve_tickets": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_engine_resolve_tickets_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_sm_configure": (C.c_int, [eng, I32]),
+        "raft_engine_sm_apply": (C.c_int, [eng, I64, I64, I32, P(raft_sm_info)]),
+        "raft_engine_sm_read": (C.c_int, [eng, I64, I64, C.c_void_p, C.c_void_p]),
+        "raft_engine_sm_write": (C.c_int, [eng, I64, I64, C.c_void_p, C.c_void_p]),
+        "raft_engine_sm_get": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_sm_check": (C.c_int, [eng, I64, I64, P(C.c_uint8), P(I64)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -413,6 +437,8 @@ EXPORTED_SYMBOLS = [
     "raft_engine_drain_committed", "raft_engine_drain_committed_dev", "raft_engine_read_applied", "raft_engine_write_applied",
     "raft_engine_read_leaders", "raft_propose_batch", "raft_propose_batch_dev", "raft_engine_resolve_tickets",
     "raft_engine_resolve_tickets_dev",
+    "raft_engine_sm_configure", "raft_engine_sm_apply", "raft_engine_sm_read", "raft_engine_sm_write",
+    "raft_engine_sm_get", "raft_engine_sm_check",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

@@ -43,22 +43,7 @@ static_assert(sizeof(raft_applied_entry) == 24 && sizeof(raft_drain_info) == 32,
 constexpr int HDR_LOST = 0, HDR_REGRESSED = 1;       // unsigned long long words of the staging header
 constexpr size_t HDR_BYTES = 256;
 
-// selected replica j of a drain of groups [g0, ...): every replica of each
-// group (replica < 0), or one replica index per group
-struct Sel {
-    int64_t g0, N;                                   // first group; selected replicas
-    int32_t replica;
-};
-
-template <int R>
-__device__ __forceinline__ int64_t sel_idx(const Sel& s, int64_t j) {
-    return s.replica < 0 ? s.g0 * R + j : (s.g0 + j) * R + s.replica;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// (the selection, Sel / sel_idx, wave_sum and by_R: raft_engine_impl.h)
 
 // pass 1.  cnt[j]: entries replica j has to deliver, cnt[N] = 0 (the scan's
 // last element is then the total).  A drain (not a peek) stores the ring skip
@@ -195,27 +180,6 @@ template <int R> struct ExpandL {
     }
 };
 
-template <template <int> class Fn, typename... A>
-void by_R(int R, A&&... a) {
-    switch (R) {
-        case 1: Fn<1>::run(a...); break;
-        case 2: Fn<2>::run(a...); break;
-        case 3: Fn<3>::run(a...); break;
-        case 4: Fn<4>::run(a...); break;
-        case 5: Fn<5>::run(a...); break;
-        case 6: Fn<6>::run(a...); break;
-        case 7: Fn<7>::run(a...); break;
-        case 8: Fn<8>::run(a...); break;
-        default: break;
-    }
-}
-
-int check_range(raft_engine* e, int64_t g0, int64_t n) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (g0 < 0 || n < 0 || g0 + n > e->p.G) return raft_internal_fail(RAFT_ERANGE, "group range outside the engine");
-    return RAFT_OK;
-}
-
 int mark(raft_engine* e, int k) {                   // a pass boundary of a timed drain
     if (!e->drain_timing) return RAFT_OK;
     HIP_TRY(hipEventRecord(e->ev_drain[k], e->stream));
@@ -226,7 +190,7 @@ int drain(raft_engine* e, int64_t g0, int64_t n, int32_t replica, raft_applied_e
           raft_drain_info* info, bool out_on_host) {
     if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (replica < -1 || replica >= e->p.R) return raft_internal_fail(RAFT_EINVAL, "replica must be -1 or in 0..R-1");
     if (max_entries < 0) return raft_internal_fail(RAFT_EINVAL, "max_entries must be >= 0");
     if (!out && max_entries > 0) return raft_internal_fail(RAFT_EINVAL, "null record buffer with max_entries > 0");
@@ -304,7 +268,7 @@ int raft_engine_drain_committed_dev(raft_engine* e, int64_t g0, int64_t n, int32
 }
 
 int raft_engine_read_applied(raft_engine* e, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
     if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));
@@ -315,7 +279,7 @@ int raft_engine_read_applied(raft_engine* e, int64_t g0, int64_t n, int32_t* out
 }
 
 int raft_engine_write_applied(raft_engine* e, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
     if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     for (int64_t k = 0; k < n * e->p.R; ++k)         // a drain reads log slots [lastApplied, hi): keep it inside the row

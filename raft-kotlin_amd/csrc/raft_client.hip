@@ -46,31 +46,7 @@ static_assert(sizeof(raft_leader_info) == 16 && sizeof(raft_ticket) == 16 && siz
 enum { CW_RANGE = 0, CW_MISS = 1, CW_INVAL = 2, CW_UNKNOWN = 3, CW_WORDS = 4 };
 constexpr size_t CW_BYTES = 256;
 
-// The group's leader as RAFT_CMD_LOWEST_LEADER chooses it: the lowest replica
-// index whose role is LEADER.  The R role words are reads of quad 0 (which
-// also holds currentTerm), all R in flight at once: unconditional loads at a
-// clamped index, as bucket_tile_kernel's.
-struct Lead {
-    int32_t r, n, term;
-};
-__device__ __forceinline__ Lead find_leader(const DevParams& p, int64_t g) {
-    const int R = p.R;
-    const int64_t base = g * R;
-    int4 q[RAFT_MAX_R];
-#pragma unroll
-    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
-    Lead l{-1, 0, 0};
-#pragma unroll
-    for (int r = RAFT_MAX_R - 1; r >= 0; --r) {                       // descending: the lowest id is taken last
-        if (r < R && q[r].z == RAFT_LEADER) {
-            l.r = r;
-            l.term = q[r].x;
-            ++l.n;
-        }
-    }
-    return l;
-}
-
+// (the group's leader, find_leader: raft_engine_impl.h)
 __global__ __launch_bounds__(BLOCK) void leaders_kernel(DevParams p, int64_t g0, int64_t n, int4* __restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (j >= n) return;

@@ -1214,6 +1214,11 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     e->drain_timing = e->drain_expanded = false;
     e->cli = e->cio = nullptr;
     e->cli_bytes = e->cio_bytes = 0;
+    e->sm = nullptr;
+    e->sm_bytes = 0;
+    e->sm_slots = 0;
+    e->ev_sm[0] = e->ev_sm[1] = nullptr;
+    e->sm_timing = false;
     e->hpart = nullptr;
     e->hpart_bytes = 0;
     e->device = device;
@@ -1396,7 +1401,10 @@ int raft_engine_destroy(raft_engine* e) {
     if (e->apo) (void)hipFree(e->apo);
     if (e->cli) (void)hipFree(e->cli);
     if (e->cio) (void)hipFree(e->cio);
+    if (e->sm) (void)hipFree(e->sm);
     for (hipEvent_t x : e->ev_drain)
+        if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_sm)
         if (x) (void)hipEventDestroy(x);
     if (e->hpart) (void)hipFree(e->hpart);
     (void)hipFree(e->base);
@@ -1650,6 +1658,7 @@ int raft_engine_reset(raft_engine* e) {
     dispatch_R<InitL>(e->p.R, e);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(e->applied, 0, e->applied_bytes, e->stream));   // nothing delivered yet
+    if (e->sm) HIP_TRY(hipMemsetAsync(e->sm, 0, e->sm_bytes, e->stream));  // a configured machine: nothing applied yet
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->bflags_host[8] = 0u;                // the step kernel's status word
     e->t = 0;
@@ -1691,7 +1700,7 @@ int raft_engine_set_step_index(raft_engine* e, int64_t t) {
 }
 int64_t raft_engine_device_bytes(raft_engine* e) {
     return e ? (int64_t)(e->bytes + e->bst_bytes + e->bio_bytes + e->aux_bytes + e->hpart_bytes + e->applied_bytes +
-                         e->apl_bytes + e->apo_bytes + e->cli_bytes + e->cio_bytes)
+                         e->apl_bytes + e->apo_bytes + e->cli_bytes + e->cio_bytes + e->sm_bytes)
              : -1;
 }
 int raft_engine_trim_staging(raft_engine* e) {

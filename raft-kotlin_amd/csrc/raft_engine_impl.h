@@ -1,9 +1,10 @@
 // raft_engine_impl.h — internal to the engine library: what raft_engine.hip
 // (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
 // batches, include/raft_engine.h raft_*_batch*), raft_apply.hip (the
-// committed-entry drain) and raft_client.hip (the leader directory, routed
-// proposals and tickets) share -- the engine object, the HBM indexing helpers,
-// a replica's quad load / store and the error / staging entry points.  Not installed.
+// committed-entry drain), raft_client.hip (the leader directory, routed
+// proposals and tickets) and raft_sm.hip (the replicated state machine)
+// share -- the engine object, the HBM indexing helpers, a replica's quad load /
+// store, the leader lookup and the error / staging entry points.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,6 +98,65 @@ __device__ __forceinline__ void store_rep(const RepState& x, const RepQuads& o, 
     if (!VOTE_ONLY && differ(q2, o.q2)) *quad(p, 2, idx) = q2;
 }
 
+// The group's leader as RAFT_CMD_LOWEST_LEADER chooses it: the lowest replica
+// index whose role is LEADER.  The R role words are reads of quad 0 (which
+// also holds currentTerm), all R in flight at once: unconditional loads at a
+// clamped index, as bucket_tile_kernel's.
+struct Lead {
+    int32_t r, n, term;
+};
+__device__ __forceinline__ Lead find_leader(const DevParams& p, int64_t g) {
+    const int R = p.R;
+    const int64_t base = g * R;
+    int4 q[RAFT_MAX_R];
+#pragma unroll
+    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
+    Lead l{-1, 0, 0};
+#pragma unroll
+    for (int r = RAFT_MAX_R - 1; r >= 0; --r) {                       // descending: the lowest id is taken last
+        if (r < R && q[r].z == RAFT_LEADER) {
+            l.r = r;
+            l.term = q[r].x;
+            ++l.n;
+        }
+    }
+    return l;
+}
+
+// ---- the selection of a drain (raft_apply.hip) or an apply (raft_sm.hip) of
+// groups [g0, ...): every replica of each group (replica < 0), or one replica
+// index per group; selected replica j is replica sel_idx(s, j)
+struct Sel {
+    int64_t g0, N;                                   // first group; selected replicas
+    int32_t replica;
+};
+
+template <int R>
+__device__ __forceinline__ int64_t sel_idx(const Sel& s, int64_t j) {
+    return s.replica < 0 ? s.g0 * R + j : (s.g0 + j) * R + s.replica;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Fn<R>::run(a...) for the engine's R (their kernels are templated on it)
+template <template <int> class Fn, typename... A>
+void by_R(int R, A&&... a) {
+    switch (R) {
+        case 1: Fn<1>::run(a...); break;
+        case 2: Fn<2>::run(a...); break;
+        case 3: Fn<3>::run(a...); break;
+        case 4: Fn<4>::run(a...); break;
+        case 5: Fn<5>::run(a...); break;
+        case 6: Fn<6>::run(a...); break;
+        case 7: Fn<7>::run(a...); break;
+        case 8: Fn<8>::run(a...); break;
+        default: break;
+    }
+}
+
 // The batch handlers report one thing: reference accesses below the window
 // (the run is then invalid, RAFT_EWINDOW).  Called in divergent control flow:
 // a mask's bit for this lane is read with ib().
@@ -174,6 +234,14 @@ struct raft_engine {
     size_t cli_bytes;
     char* cio;
     size_t cio_bytes;
+    // the replicated state machine (raft_sm.hip), opt-in: nullptr until raft_engine_sm_configure.  One
+    // allocation: a 4-KB header (the totals of an apply, striped), the heads [G * R] of 16 bytes (applied, lost,
+    // hash), the registers [G * R][sm_slots] uint32.  Not staging: trim_staging keeps it
+    char* sm;
+    size_t sm_bytes;
+    int sm_slots;
+    hipEvent_t ev_sm[2];        // around the last apply kernel while sm_timing (scripts/sm_probe.py)
+    bool sm_timing;
     int64_t* counters_dev;      // [K][STRIDE] scratch
     unsigned long long* accum;  // [K * NC] counter accumulators: sum + chunks done << 48 (zero between launches)
     // step-kernel event timing
@@ -185,3 +253,12 @@ struct raft_engine {
     size_t ev_used;
     int64_t timed_launches;     // K-step launches of the whole grid timed since the last kernel_time()
 };
+
+namespace {
+// groups [g0, g0 + n) of a non-null engine (the accessors of raft_apply.hip and raft_sm.hip)
+inline int check_groups(raft_engine* e, int64_t g0, int64_t n) {
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (g0 < 0 || n < 0 || g0 + n > e->p.G) return raft_internal_fail(RAFT_ERANGE, "group range outside the engine");
+    return RAFT_OK;
+}
+}  // namespace

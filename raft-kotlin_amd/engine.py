@@ -407,6 +407,103 @@ class RaftEngine:
                                                                              out_ptr, int(n)),
                                    "raft_engine_resolve_tickets_dev")
 
+    # -- the replicated state machine (raft_engine_sm_*) -------------------------
+    @property
+    def sm_slots(self) -> int:
+        """Registers per replica of the configured state machine (0: none)."""
+        return getattr(self, "_sm_slots", 0)
+
+    def sm_configure(self, slots: int):
+        """Allocate and zero the state machine with `slots` registers per
+        replica (a power of two in 1..64; again: zero it or resize it); 0 frees it."""
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or (slots != 0 and slots not in abi.SM_SLOTS):
+            raise ValueError(f"sm_configure: slots must be 0 or a power of two in 1..64, not {slots!r}")
+        self._check(self._lib.raft_engine_sm_configure(self._h, int(slots)), "sm_configure")
+        self._sm_slots = int(slots)
+
+    def sm_apply(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
+        """Apply the entries of groups [g0, g0 + n) (replica -1: every replica,
+        else that replica index) that became committed since each machine's
+        cursor, on the device: info with applied, lost, regressed, status.
+        RAFT_EWINDOW (entries left the log window unapplied) is not raised: the
+        call did everything else and info["status"] carries the code."""
+        g0, n, replica = self._drain_args(g0, n, replica, None, "sm_apply")
+        si = abi.raft_sm_info()
+        rc = self._lib.raft_engine_sm_apply(self._h, g0, n, replica, C.byref(si))
+        if rc != abi.RAFT_EWINDOW:
+            self._check(rc, "sm_apply")
+        return {"applied": int(si.applied), "lost": int(si.lost), "regressed": int(si.regressed), "status": int(rc)}
+
+    def sm_read(self, g0: int = 0, n: int | None = None, regs: bool = True):
+        """The machines of groups [g0, g0 + n): (heads, regs) -- heads [n, R] of
+        abi.SM_HEAD_DTYPE (applied, lost, hash), regs [n, R, slots] uint32 (None
+        with regs=False)."""
+        n = self.G - g0 if n is None else n
+        h = np.zeros((max(int(n), 0), self.R), dtype=abi.SM_HEAD_DTYPE)   # a bad range is the library's to refuse
+        r = np.zeros((max(int(n), 0), self.R, self.sm_slots), dtype=np.uint32) if regs and self.sm_slots else None
+        self._check(self._lib.raft_engine_sm_read(self._h, int(g0), int(n), C.c_void_p(h.ctypes.data),
+                                                  C.c_void_p(r.ctypes.data) if r is not None else None), "sm_read")
+        return h, r
+
+    def sm_write(self, heads=None, regs=None, g0: int = 0):
+        """Store the machines of groups [g0, g0 + n) (resuming a run): heads
+        [n, R] of abi.SM_HEAD_DTYPE with applied in 0..log_cap and lost >= 0,
+        regs an integer [n, R, slots] array; either may be None."""
+        if heads is None and regs is None:
+            raise ValueError("sm_write: heads or regs is required")
+        n = None
+        if heads is not None:
+            heads = np.ascontiguousarray(heads)
+            if heads.dtype != abi.SM_HEAD_DTYPE or heads.ndim != 2 or heads.shape[1] != self.R:
+                raise ValueError(f"sm_write: heads must be abi.SM_HEAD_DTYPE records of shape (n, {self.R})")
+            if heads.size and (heads["applied"].min() < 0 or heads["applied"].max() > self.cap or heads["lost"].min() < 0):
+                raise ValueError(f"sm_write: every applied must be in 0..{self.cap} and every lost >= 0")
+            n = heads.shape[0]
+        if regs is not None:
+            regs = np.asarray(regs)
+            if regs.ndim != 3 or regs.shape[1:] != (self.R, self.sm_slots) or regs.dtype.kind not in "iu":
+                raise ValueError(f"sm_write: regs {regs.shape} {regs.dtype} must be an integer array of shape "
+                                 f"(n, {self.R}, {self.sm_slots})")
+            if n is not None and regs.shape[0] != n:
+                raise ValueError(f"sm_write: heads hold {n} groups and regs {regs.shape[0]}")
+            n = regs.shape[0]
+            regs = np.ascontiguousarray(regs, dtype=np.uint32)
+        self._check(self._lib.raft_engine_sm_write(self._h, int(g0), n,
+                                                   C.c_void_p(heads.ctypes.data) if heads is not None else None,
+                                                   C.c_void_p(regs.ctypes.data) if regs is not None else None), "sm_write")
+
+    def sm_get(self, groups, keys, replica=-1) -> np.ndarray:
+        """The batched client read: register keys[m] (its low bits name the
+        slot) of groups[m], from `replica` (one index for all, or one per
+        request; -1: the group's leader).  Returns abi.SM_VALUE_DTYPE records:
+        value, the replica read (-1 and value 0 without a leader), its applied
+        cursor and its commitIndex."""
+        g, k = self._client_arrays(groups, keys, "sm_get")
+        r = np.asarray(replica)
+        if r.ndim == 0:
+            r = np.full(g.shape, r)
+        if r.dtype.kind not in "iu" or r.shape != g.shape:
+            raise ValueError(f"sm_get: replica must be an integer or {g.shape[0]} integers")
+        if r.size and (r.min() < -1 or r.max() >= self.R):
+            raise ValueError(f"sm_get: every replica must be -1 (the leader) or in 0..{self.R - 1}")
+        r = np.ascontiguousarray(r, dtype=np.int32)
+        out = np.zeros(g.shape[0], dtype=abi.SM_VALUE_DTYPE)
+        self._check(self._lib.raft_engine_sm_get(self._h, C.c_void_p(g.ctypes.data), C.c_void_p(r.ctypes.data),
+                                                 C.c_void_p(k.ctypes.data), C.c_void_p(out.ctypes.data), g.shape[0]),
+                    "sm_get")
+        return out
+
+    def sm_check(self, g0: int = 0, n: int | None = None, flags: bool = False):
+        """State Machine Safety: groups with two replicas that lost nothing,
+        applied equally many entries and hold different hashes; returns the
+        count, or (count, per-group uint8 flags) with flags=True."""
+        n = self.G - g0 if n is None else n
+        f = np.zeros(max(int(n), 0), dtype=np.uint8) if flags else None
+        out = C.c_int64()
+        self._check(self._lib.raft_engine_sm_check(self._h, int(g0), int(n), abi.ptr(f, C.c_uint8) if flags else None,
+                                                   C.byref(out)), "sm_check")
+        return (int(out.value), f) if flags else int(out.value)
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

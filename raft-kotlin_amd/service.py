@@ -15,6 +15,9 @@ argument meaning and error behaviour:
   (RaftServer.kt:96-97)
 * ``lastApplied`` (RaftServer.kt:47) and ``RaftService.poll_committed``: the
   entries that became committed since the last poll, for a state machine to apply
+* ``RaftService.apply_committed`` / ``read`` and ``RaftNode.machine``: the
+  replicated state machine on the device -- committed entries applied where
+  they are, a register read routed to the leader, a node's head and registers
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -89,6 +92,10 @@ class CommandTable:
             self._names[i] = s
         return i
 
+    def lookup(self, s: str) -> Optional[int]:
+        """The id of a string interned before, or None: never grows the table."""
+        return self._ids.get(s)
+
     def name(self, i: int) -> str:
         # commands injected by the lockstep harness carry Philox ids
         return self._names.get(int(i), f"cmd#{int(i):08x}")
@@ -150,6 +157,12 @@ class RaftNode:
         """Entries [0, lastApplied) of this node's log were handed out by poll_committed."""
         return int(self.s.engine.applied(self.group, 1)[0, self.replica])
 
+    def machine(self) -> tuple:
+        """This node's state machine: (head, registers) -- head a record of
+        abi.SM_HEAD_DTYPE (applied, lost, hash), registers [slots] uint32."""
+        h, r = self.s.engine.sm_read(self.group, 1)
+        return h[0, self.replica], r[0, self.replica]
+
 
 class RaftService:
     """The `service Raft` surface of every node of a RaftEngine."""
@@ -197,6 +210,31 @@ class RaftService:
         return ((g, r, i, t, name(c)) for g, r, i, t, c in
                 zip(rec["group"].tolist(), rec["replica"].tolist(), rec["index"].tolist(), rec["term"].tolist(),
                     rec["cmd"].tolist()))
+
+    # -- the replicated state machine: committed entries applied on the device ---
+    def apply_committed(self, g0: int = 0, n: Optional[int] = None, replica: int = -1) -> dict:
+        """Apply every entry of groups [g0, g0 + n) that became committed since
+        the machines' cursors (engine.sm_configure first): one kernel, no copy to
+        the host.  Returns the info (applied, lost, regressed, status).  A string
+        command lands in the register its interned id's low bits name."""
+        return self.engine.sm_apply(g0, n, replica)
+
+    def read(self, groups, keys: List[str], replica=-1) -> List[tuple]:
+        """The client's read: per request (command, replica, applied, commit) --
+        the command last applied to the register that keys[m] maps to (its
+        interned id's low bits; named by CommandTable.name), on `replica` of
+        groups[m] (-1: the group's leader; replica -1 back: it has none), with
+        that replica's applied cursor and commitIndex.  A read changes nothing:
+        a key that was never interned has no id, hence no register; it raises
+        KeyError before any device call."""
+        ids = [self.commands.lookup(k) for k in keys]
+        unknown = [k for k, i in zip(keys, ids) if i is None]
+        if unknown:
+            raise KeyError(f"read: never submitted, so no register holds it: {unknown[0]!r}")
+        v = self.engine.sm_get(groups, ids, replica)
+        name = self.commands.name
+        return [(name(c), r, a, m) for c, r, a, m in
+                zip(v["value"].tolist(), v["replica"].tolist(), v["applied"].tolist(), v["commit"].tolist())]
 
     # -- the client path: /cmd/{command} (RaftServer.kt:87-88) with an answer ---
     def leader(self, group: int) -> Optional[RaftNode]:
