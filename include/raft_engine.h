@@ -45,8 +45,9 @@ extern "C" {
  * raft_engine_reset, raft_engine_wait_stream.  Added since without a new
  * version, because nothing that existed changed: committed-entry delivery
  * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied), the
- * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*)
- * and the replicated state machine (raft_engine_sm_*) */
+ * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*),
+ * the replicated state machine (raft_engine_sm_*) and replica restart
+ * (raft_engine_restart*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -654,6 +655,80 @@ int raft_engine_sm_get(raft_engine* e, const int64_t* group, const int32_t* repl
  * (quirks Q4, Q9), RAFT_MODE_TEXTBOOK must not. */
 int raft_engine_sm_check(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, int64_t* diverged);
 
+/* ---- replica crash and restart: volatile state lost on the device -----------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The reference's counterpart is killing a node's JVM and launching it again
+ * (main, RaftServer.kt:302-310): it persists nothing, so the new process
+ * starts from RaftServer.kt:35-48.  Here one kernel resets the chosen replicas
+ * in HBM, between two step launches, without a copy of the state to the host,
+ * and the caller says how much the process kept on disk.
+ *
+ * A restarted replica r, in terms of the canonical export (read_state):
+ * - role = FOLLOWER, commitIndex = 0, phaseMs = retryMs = 0;
+ * - flags = RAFT_FL_ARMED alone, what raft_engine_create leaves: no election,
+ *   backoff, heartbeat session, pending-vote, votes or latch bits;
+ * - rows next[r][*] and match[r][*] = 0, what raft_engine_create leaves;
+ * - electionMs = a fresh timeout by the rule of a handler batch's timer reset:
+ *   the replica's RAFT_RNG_TIMER word at the engine's current step index,
+ *   scaled to election_min_ms..election_max_ms;
+ * - flags 0: currentTerm, votedFor, lastIndex, physLen and the log are kept
+ *   (the Raft paper's persistent state), and so are lastApplied and the
+ *   machine: a durable consumer.  The drain and sm_apply then see
+ *   min(commit, last) < cursor, count the replica in `regressed` and go on once
+ *   its commitIndex has caught up;
+ * - RAFT_RESTART_REPLAY: also lastApplied = 0 and, if a machine is configured,
+ *   its head (applied, lost, hash) and registers = 0;
+ * - RAFT_RESTART_AMNESIA: also currentTerm = 0, votedFor = -1, lastIndex =
+ *   physLen = 0 (the row's slots are not cleared: slots at or beyond physLen are
+ *   unspecified), and everything REPLAY does.
+ * No other replica changes: the pending-vote bits others hold towards r stay.
+ * The engine's own mirrors (the log-tail cache, the session rows' placement)
+ * end up as a write_state of the same words would leave them, without the
+ * engine-wide cache rebuild a write_state causes.
+ *
+ * Selection, over groups [g0, g0 + n):
+ * - a mask of n bytes: bit r of mask[j] restarts replica r of group g0 + j
+ *   (bits at or above R are ignored); host memory, or with _dev device memory
+ *   under the buffer rules of raft_*_batch_dev;
+ * - _random: replica r of global group id gid restarts when
+ *   w < ceil(ppm * 2^32 / 10^6), w the RAFT_RNG_RESTART word of (step index,
+ *   gid, r): 10^6 ppm selects every replica, 0 none.  Nothing is read from the
+ *   host, and the same seed and step index select the same replicas.
+ *
+ * down_steps > 0 (at most 2^23 - 1): every group with a restarted replica gets
+ * its isolation word (RAFT_GROUP_EXTRA[0]) set to down_steps << 8 | its lowest
+ * restarted replica, over an isolation already running.  This is the harness's
+ * isolation (churn_ppm), not a frozen process: for down_steps steps that replica
+ * is cut off in both directions while its timers keep running, and at most one
+ * replica per group can be down.  down_steps = 0 leaves the word alone.
+ *
+ * Not promised: RAFT_RESTART_AMNESIA forgets votes and log entries that other
+ * replicas counted on, so RAFT_C_DUAL_LEADER_GROUPS, raft_engine_check_log_matching
+ * and raft_engine_sm_check may report violations afterwards in either mode.
+ *
+ * Ordering is the drain's: the call runs on the engine stream, sees every step
+ * enqueued before it, later step launches wait for it, and it returns when its
+ * kernel has finished.
+ * RAFT_EINVAL: null engine or info, a null mask with n > 0, unknown flag bits,
+ * down_steps outside 0..2^23-1; RAFT_ERANGE: groups outside the engine.  n == 0
+ * is RAFT_OK with a zeroed info. */
+#define RAFT_RESTART_AMNESIA 1   /* also forget currentTerm, votedFor and the log (the reference persists nothing) */
+#define RAFT_RESTART_REPLAY  2   /* also zero the consumers: lastApplied and, if configured, the machine
+                                    (Raft Fig. 2: lastApplied is volatile; the log is replayed from 0) */
+typedef struct raft_restart_info {  /* 32 bytes */
+    int64_t restarted;        /* replicas restarted */
+    int64_t leaders;          /* of those, the ones whose role was LEADER */
+    int64_t entries_dropped;  /* AMNESIA: sum of their lastIndex before the call, else 0 */
+    int64_t reserved;         /* 0 */
+} raft_restart_info;
+int raft_engine_restart       (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_host,
+                               int32_t flags, int32_t down_steps, raft_restart_info* info);
+int raft_engine_restart_dev   (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev,
+                               int32_t flags, int32_t down_steps, raft_restart_info* info);
+int raft_engine_restart_random(raft_engine* e, int64_t g0, int64_t n, uint32_t ppm,
+                               int32_t flags, int32_t down_steps, raft_restart_info* info);
+
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages
  * to the same (group, dst) are applied in batch order.  Effects on the
@@ -716,6 +791,8 @@ int raft_engine_set_batch_path(raft_engine* e, int32_t path);
 #define RAFT_RNG_APPEND_DROP  4u  /* sub = src | chunk << 8                        */
 #define RAFT_RNG_HARNESS      5u  /* sub = 0: w0 churn, w1 command, w2 command id  */
 #define RAFT_RNG_PARTITION    6u  /* c0 = partition window start, sub = 0: w0 mask */
+#define RAFT_RNG_RESTART      7u  /* c0 = step index at the call, sub = replica >> 2, word
+                                     replica & 3: raft_engine_restart_random's selection */
 #define RAFT_RNG_INIT_STEP    0xFFFFFFFFu  /* c0 of the initial timer draws        */
 void raft_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

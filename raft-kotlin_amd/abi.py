@@ -230,6 +230,17 @@ SM_VALUE_DTYPE = np.dtype([("value", np.uint32), ("replica", np.int32), ("applie
 SM_SLOTS = (1, 2, 4, 8, 16, 32, 64)      # raft_engine_sm_configure: registers per replica
 
 
+class raft_restart_info(C.Structure):
+    _fields_ = [("restarted", C.c_int64), ("leaders", C.c_int64), ("entries_dropped", C.c_int64),
+                ("reserved", C.c_int64)]
+
+
+# raft_engine_restart*: flags, the largest down_steps, the Philox purposes (RAFT_RNG_*)
+RESTART_AMNESIA, RESTART_REPLAY = 1, 2
+RESTART_MAX_DOWN_STEPS = (1 << 23) - 1
+RNG_TIMER, RNG_RESTART = 1, 7
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -383,6 +394,9 @@ def load_library(path: str | None = None):
         "raft_engine_sm_write": (C.c_int, [eng, I64, I64, C.c_void_p, C.c_void_p]),
         "raft_engine_sm_get": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_engine_sm_check": (C.c_int, [eng, I64, I64, P(C.c_uint8), P(I64)]),
+        "raft_engine_restart": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
+        "raft_engine_restart_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
+        "raft_engine_restart_random": (C.c_int, [eng, I64, I64, C.c_uint32, I32, I32, P(raft_restart_info)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -439,6 +453,7 @@ EXPORTED_SYMBOLS = [
     "raft_engine_resolve_tickets_dev",
     "raft_engine_sm_configure", "raft_engine_sm_apply", "raft_engine_sm_read", "raft_engine_sm_write",
     "raft_engine_sm_get", "raft_engine_sm_check",
+    "raft_engine_restart", "raft_engine_restart_dev", "raft_engine_restart_random",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

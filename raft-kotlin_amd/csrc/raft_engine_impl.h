@@ -2,8 +2,8 @@
 // (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
 // batches, include/raft_engine.h raft_*_batch*), raft_apply.hip (the
 // committed-entry drain), raft_client.hip (the leader directory, routed
-// proposals and tickets) and raft_sm.hip (the replicated state machine)
-// share -- the engine object, the HBM indexing helpers, a replica's quad load /
+// proposals and tickets), raft_sm.hip (the replicated state machine) and
+// raft_fault.hip (replica restart) share -- the engine object, the HBM indexing helpers, a replica's quad load /
 // store, the leader lookup and the error / staging entry points.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -261,4 +261,9 @@ inline int check_groups(raft_engine* e, int64_t g0, int64_t n) {
     if (g0 < 0 || n < 0 || g0 + n > e->p.G) return raft_internal_fail(RAFT_ERANGE, "group range outside the engine");
     return RAFT_OK;
 }
+// the machine's allocation (raft_engine::sm, raft_sm.hip): a header of SM_HDR_BYTES, the heads [G * R] (int4:
+// applied, lost, hash lo, hash hi), the registers [G * R][sm_slots]; raft_fault.hip zeroes a restarted replica's
+constexpr size_t SM_HDR_BYTES = 4096;
+inline int4* sm_heads_of(raft_engine* e) { return (int4*)(e->sm + SM_HDR_BYTES); }
+inline uint32_t* sm_regs_of(raft_engine* e) { return (uint32_t*)(e->sm + SM_HDR_BYTES + al256((size_t)e->dp.GR * 16)); }
 }  // namespace

@@ -54,12 +54,13 @@ static_assert(sizeof(raft_sm_info) == 32 && sizeof(raft_sm_head) == 16 && sizeof
 // entries adds to `applied`, and on one word the atomics of every wave of a large engine serialise
 constexpr int HDR_APPLIED = 0, HDR_LOST = 1, HDR_REGRESSED = 2, HDR_LINE = 8, HDR_STRIPES = 64;
 constexpr size_t HDR_BYTES = (size_t)HDR_STRIPES * HDR_LINE * 8;
+static_assert(HDR_BYTES == SM_HDR_BYTES, "the header's size is shared with raft_fault.hip (raft_engine_impl.h)");
 constexpr uint64_t SM_P = 0xD1342543DE82EF95ull, SM_GOLD = 0x9E3779B97F4A7C15ull;
 constexpr int PW_WORDS = 66;                                          // P^0 .. P^64 and a pad word, per wave
 
 // the machine's allocation: header, heads (int4: applied, lost, hash lo, hash hi), registers
-int4* heads_of(raft_engine* e) { return (int4*)(e->sm + HDR_BYTES); }
-uint32_t* regs_of(raft_engine* e) { return (uint32_t*)(e->sm + HDR_BYTES + al256((size_t)e->dp.GR * 16)); }
+int4* heads_of(raft_engine* e) { return sm_heads_of(e); }
+uint32_t* regs_of(raft_engine* e) { return sm_regs_of(e); }
 
 __device__ __forceinline__ uint64_t sm_x(int32_t i, uint32_t t, uint32_t c) {
     uint64_t z = ((uint64_t)t << 32 | c) + (uint64_t)(uint32_t)i * SM_GOLD;

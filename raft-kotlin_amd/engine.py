@@ -504,6 +504,70 @@ class RaftEngine:
                                                    C.byref(out)), "sm_check")
         return (int(out.value), f) if flags else int(out.value)
 
+    # -- replica crash and restart (raft_engine_restart*) -------------------------
+    def _restart_args(self, g0, n, amnesia, replay, down_steps, what: str):
+        """The arguments every restart form shares, checked before any library call."""
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n), ("down_steps", down_steps)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
+        if not 0 <= down_steps <= abi.RESTART_MAX_DOWN_STEPS:
+            raise ValueError(f"{what}: down_steps must be in 0..{abi.RESTART_MAX_DOWN_STEPS}")
+        flags = (abi.RESTART_AMNESIA if amnesia else 0) | (abi.RESTART_REPLAY if replay else 0)
+        return int(g0), int(n), flags, int(down_steps)
+
+    @staticmethod
+    def _restart_info(ri: "abi.raft_restart_info") -> dict:
+        return {"restarted": int(ri.restarted), "leaders": int(ri.leaders), "entries_dropped": int(ri.entries_dropped)}
+
+    def restart(self, mask=None, *, ppm: int | None = None, g0: int = 0, n: int | None = None,
+                amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
+        """Crash and restart replicas of groups [g0, g0 + n) on the device: they
+        come back as FOLLOWERs with commitIndex 0, no election or heartbeat
+        session and a fresh election timeout.  Exactly one of `mask` (n bytes,
+        bit r of mask[j]: replica r of group g0 + j) and `ppm` (a seeded rate per
+        replica, drawn at the current step index) selects them.  By default
+        currentTerm, votedFor and the log are kept and so are lastApplied and
+        the machine; replay=True also zeroes those consumers; amnesia=True also
+        forgets term, vote and log.  down_steps > 0 isolates the lowest
+        restarted replica of each group for that many steps (the harness's
+        isolation: cut off, timers running).  Returns restarted, leaders,
+        entries_dropped (include/raft_engine.h raft_restart_info)."""
+        if (mask is None) == (ppm is None):
+            raise ValueError("restart: exactly one of mask and ppm is required")
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
+                raise ValueError(f"restart: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
+            n = m.shape[0] if n is None else n
+            if m.shape[0] != n:
+                raise ValueError(f"restart: mask holds {m.shape[0]} groups, n is {n}")
+            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
+        elif not isinstance(ppm, (int, np.integer)) or isinstance(ppm, bool) or not 0 <= ppm <= 0xFFFFFFFF:
+            raise ValueError(f"restart: ppm must be an integer in 0..2^32-1, not {ppm!r}")
+        g0, n, flags, down_steps = self._restart_args(g0, n, amnesia, replay, down_steps, "restart")
+        ri = abi.raft_restart_info()
+        if mask is not None:
+            rc = self._lib.raft_engine_restart(self._h, g0, n, C.c_void_p(m.ctypes.data), flags, down_steps, C.byref(ri))
+        else:
+            rc = self._lib.raft_engine_restart_random(self._h, g0, n, int(ppm), flags, down_steps, C.byref(ri))
+        self._check(rc, "raft_engine_restart" if mask is not None else "raft_engine_restart_random")
+        return self._restart_info(ri)
+
+    def restart_dev(self, mask_ptr: int, *, g0: int = 0, n: int | None = None, amnesia: bool = False,
+                    replay: bool = False, down_steps: int = 0, after_stream: int | None = None) -> dict:
+        """restart with the mask in DEVICE memory (n bytes on this engine's GPU,
+        e.g. a torch uint8 tensor's data_ptr()); returns once the kernel finished."""
+        g0, n, flags, down_steps = self._restart_args(g0, n, amnesia, replay, down_steps, "restart_dev")
+        if n > 0 and not mask_ptr:
+            raise ValueError("restart_dev: a device mask is required")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        ri = abi.raft_restart_info()
+        self._check(self._lib.raft_engine_restart_dev(self._h, g0, n, C.c_void_p(mask_ptr or 0), flags, down_steps,
+                                                      C.byref(ri)), "raft_engine_restart_dev")
+        return self._restart_info(ri)
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

@@ -157,6 +157,12 @@ class RaftNode:
         """Entries [0, lastApplied) of this node's log were handed out by poll_committed."""
         return int(self.s.engine.applied(self.group, 1)[0, self.replica])
 
+    def restart(self, amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
+        """Kill this node's process and launch it again (main, RaftServer.kt:302-310).
+        amnesia=True is what the reference does, since it persists nothing:
+        entries() is empty and currentTerm is 0 afterwards."""
+        return self.s.restart([self.group], [self.replica], amnesia=amnesia, replay=replay, down_steps=down_steps)
+
     def machine(self) -> tuple:
         """This node's state machine: (head, registers) -- head a record of
         abi.SM_HEAD_DTYPE (applied, lost, hash), registers [slots] uint32."""
@@ -235,6 +241,24 @@ class RaftService:
         name = self.commands.name
         return [(name(c), r, a, m) for c, r, a, m in
                 zip(v["value"].tolist(), v["replica"].tolist(), v["applied"].tolist(), v["commit"].tolist())]
+
+    # -- crash and restart: the JVM of a node killed and relaunched (RaftServer.kt:302-310) ---
+    def restart(self, groups, replicas, amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
+        """Restart node replicas[m] of groups[m], all in one device call (a
+        node named twice restarts once): the mask of RaftEngine.restart over
+        the span of the named groups.  Returns its info."""
+        g = np.asarray(groups, dtype=np.int64).reshape(-1)
+        r = np.asarray(replicas, dtype=np.int64).reshape(-1)
+        if g.shape != r.shape:
+            raise ValueError(f"restart: groups {g.shape} and replicas {r.shape} must be of one length")
+        if g.size == 0:
+            return {"restarted": 0, "leaders": 0, "entries_dropped": 0}
+        if g.min() < 0 or g.max() >= self.engine.G or r.min() < 0 or r.max() >= self.engine.R:
+            raise IndexError("restart: a node outside the engine")
+        g0 = int(g.min())
+        mask = np.zeros(int(g.max()) - g0 + 1, dtype=np.uint8)
+        np.bitwise_or.at(mask, g - g0, (1 << r).astype(np.uint8))
+        return self.engine.restart(mask, g0=g0, amnesia=amnesia, replay=replay, down_steps=down_steps)
 
     # -- the client path: /cmd/{command} (RaftServer.kt:87-88) with an answer ---
     def leader(self, group: int) -> Optional[RaftNode]:
