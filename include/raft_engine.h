@@ -46,8 +46,9 @@ extern "C" {
  * version, because nothing that existed changed: committed-entry delivery
  * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied), the
  * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*),
- * the replicated state machine (raft_engine_sm_*) and replica restart
- * (raft_engine_restart*) */
+ * the replicated state machine (raft_engine_sm_*), replica restart
+ * (raft_engine_restart*) and linearizable reads (raft_read_begin_batch*,
+ * raft_read_serve_batch*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -728,6 +729,116 @@ int raft_engine_restart_dev   (raft_engine* e, int64_t g0, int64_t n, const uint
                                int32_t flags, int32_t down_steps, raft_restart_info* info);
 int raft_engine_restart_random(raft_engine* e, int64_t g0, int64_t n, uint32_t ppm,
                                int32_t flags, int32_t down_steps, raft_restart_info* info);
+
+/* ---- linearizable reads: ReadIndex tickets confirmed on the device ----------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * raft_engine_sm_get reads "the group's leader" as raft_leader_info.leader
+ * chooses it and says how far that replica has applied.  That is a best-effort
+ * read: an isolated leader keeps the role LEADER for many steps after the rest
+ * of the group elected a successor in a higher term, it is often the lowest
+ * id, and its applied == commit looks perfectly fresh; a freshly elected
+ * leader's commitIndex can lag behind writes a client already saw COMMITTED.
+ * The pair below is Raft's ReadIndex protocol (Ongaro's thesis §6.4), shaped
+ * like propose / resolve: begin hands out a ticket (which leader, which term,
+ * how far it had committed), serve confirms the ticket and reads.  Both calls
+ * are read-only on the canonical state, the logs, the digest, lastApplied and
+ * the machine.
+ *
+ * Begin: message m asks for a read index in group[m].
+ * - The leader L is the replica with role LEADER that has the highest
+ *   currentTerm, the lowest index among equals.  Not raft_leader_info.leader's
+ *   rule: a deposed leader at a lower index must not shadow its successor.
+ * - T = currentTerm_L and hi = clamp(min(commitIndex_L, lastIndex_L), 0,
+ *   log_cap): the committed prefix the drain and sm_apply use.
+ * - The ticket, first match wins:
+ *     no replica is LEADER                         (-1, 0, -1, NO_LEADER)
+ *     log_window only: hi > 0 and slot hi - 1 of L
+ *       is below its window (hi - 1 < physLen_L - W)
+ *       (hi == 0 names no slot: never UNKNOWN)     (L, T, hi, UNKNOWN); not read
+ *     hi == 0 or log_L[hi - 1].term != T           (L, T, hi, TERM_UNCOMMITTED)
+ *     otherwise                                    (L, T, hi, ISSUED)
+ *   TERM_UNCOMMITTED: L has not yet committed an entry of its own term, so its
+ *   commitIndex may lag behind acknowledged writes.  This engine has no no-op
+ *   entry: a client command must commit first, and the client begins again.
+ * - A group outside the engine fails the whole batch with RAFT_ERANGE before any
+ *   ticket is written, as raft_propose_batch does.  n == 0 is RAFT_OK.  n < 2^31.
+ *   RAFT_EWINDOW if any ticket is UNKNOWN, after filling every ticket.
+ * - The machine need not be configured.
+ *
+ * Serve: out[m] = register key[m] of the replica ticket[m] names in group[m],
+ * if the ticket still holds.  Needs raft_engine_sm_configure (else
+ * RAFT_EINVAL, like every raft_engine_sm_* call).  Every record is filled;
+ * first match wins:
+ *   INVALID    group outside the engine, replica outside 0..R-1 or read_index
+ *              outside 0..log_cap (a NO_LEADER ticket, with its -1s, included:
+ *              serve what begin ISSUED); nothing is read
+ *   NONE       the ticket's status is not ISSUED
+ *   DEPOSED    the ticket's replica no longer has role LEADER with
+ *              currentTerm == ticket.term; the client begins again
+ *   NO_QUORUM  agree < R / 2 + 1, where agree counts the group's replicas (the
+ *              ticket's included) whose currentTerm == ticket.term
+ *   BEHIND     the replica's machine has applied < read_index; the caller runs
+ *              raft_engine_sm_apply and serves again
+ *   GAPPED     the machine's lost != 0: its registers are not the fold of the log
+ *   SERVED     value = reg[key & (S - 1)] of that replica
+ * agree is filled from DEPOSED on, applied (the replica's cursor) from BEHIND
+ * on, value in SERVED; every other word is 0.
+ * Returns RAFT_ERANGE if any group was out of range, otherwise RAFT_EINVAL if
+ * any ticket had a bad replica or read_index (also: null engine, not
+ * configured, n < 0 or n >= 2^31, a null buffer with n > 0, and then nothing is
+ * filled), otherwise RAFT_OK.
+ *
+ * Why the quorum check is enough.  A leader of a term above T needs votes
+ * from a majority whose terms are then above T; that majority would intersect
+ * the majority found at exactly T.  So at the instant of the serve L is the
+ * newest leader.  Once L has committed an entry of its own term (ISSUED), its
+ * committed prefix at begin covered every write acknowledged before begin, and
+ * the machine has applied at least that far.  The confirmation is the engine
+ * reading the replicas' term words in HBM: a lossless, instantaneous
+ * heartbeat round.  Drops, partitions and the isolation word are deliberately
+ * not consulted: they decide how long an isolated leader can still serve,
+ * never safety.
+ *
+ * Not promised: in RAFT_MODE_REFERENCE quirks Q4 and Q9 let committed entries
+ * vanish, as the drain, the tickets and the machine already say, and
+ * RAFT_RESTART_AMNESIA forgets votes and entries.  Promised in
+ * RAFT_MODE_TEXTBOOK with a flat log and no amnesia.
+ *
+ * Ordering as the client path's: each call runs on the engine stream, sees
+ * every step enqueued before it, later step launches wait for it, and it
+ * returns when its kernel has finished.  The _dev forms take DEVICE pointers
+ * under the buffer rules of raft_*_batch_dev; ticket and out must be 16-byte
+ * aligned. */
+#define RAFT_READ_ISSUED           0
+#define RAFT_READ_TERM_UNCOMMITTED 1  /* the leader has committed no entry of its own term yet */
+#define RAFT_READ_NO_LEADER        2  /* no replica of the group is LEADER */
+#define RAFT_READ_UNKNOWN          3  /* log_window only: the slot that decides is below the leader's window */
+typedef struct raft_read_ticket {     /* 16 bytes */
+    int32_t replica;     /* the leader chosen, -1 for NO_LEADER */
+    int32_t term;        /* its currentTerm, 0 for NO_LEADER */
+    int32_t read_index;  /* its committed prefix: entries [0, read_index) must be applied before the read; -1 for NO_LEADER */
+    int32_t status;      /* one of the four above */
+} raft_read_ticket;
+#define RAFT_READ_SERVED    0
+#define RAFT_READ_BEHIND    1
+#define RAFT_READ_GAPPED    2
+#define RAFT_READ_NO_QUORUM 3
+#define RAFT_READ_DEPOSED   4
+#define RAFT_READ_NONE      5
+#define RAFT_READ_INVALID   6
+typedef struct raft_read_result {     /* 16 bytes */
+    uint32_t value;
+    int32_t  status;     /* one of the seven above */
+    int32_t  applied;
+    int32_t  agree;
+} raft_read_result;
+int raft_read_begin_batch    (raft_engine* e, const int64_t* group, raft_read_ticket* ticket, int64_t n);
+int raft_read_begin_batch_dev(raft_engine* e, const int64_t* group, raft_read_ticket* ticket, int64_t n);
+int raft_read_serve_batch    (raft_engine* e, const int64_t* group, const raft_read_ticket* ticket, const uint32_t* key,
+                              raft_read_result* out, int64_t n);
+int raft_read_serve_batch_dev(raft_engine* e, const int64_t* group, const raft_read_ticket* ticket, const uint32_t* key,
+                              raft_read_result* out, int64_t n);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

@@ -241,6 +241,24 @@ RESTART_MAX_DOWN_STEPS = (1 << 23) - 1
 RNG_TIMER, RNG_RESTART = 1, 7
 
 
+class raft_read_ticket(C.Structure):
+    _fields_ = [("replica", C.c_int32), ("term", C.c_int32), ("read_index", C.c_int32), ("status", C.c_int32)]
+
+
+class raft_read_result(C.Structure):
+    _fields_ = [("value", C.c_uint32), ("status", C.c_int32), ("applied", C.c_int32), ("agree", C.c_int32)]
+
+
+# linearizable reads: the records as numpy records (16 bytes each, no padding), raft_read_ticket.status and
+# raft_read_result.status (RAFT_READ_*)
+READ_TICKET_DTYPE = np.dtype([("replica", np.int32), ("term", np.int32), ("read_index", np.int32), ("status", np.int32)])
+READ_RESULT_DTYPE = np.dtype([("value", np.uint32), ("status", np.int32), ("applied", np.int32), ("agree", np.int32)])
+READ_ISSUED, READ_TERM_UNCOMMITTED, READ_NO_LEADER, READ_UNKNOWN = 0, 1, 2, 3
+READ_TICKET_STATUS_NAMES = ["ISSUED", "TERM_UNCOMMITTED", "NO_LEADER", "UNKNOWN"]
+READ_SERVED, READ_BEHIND, READ_GAPPED, READ_NO_QUORUM, READ_DEPOSED, READ_NONE, READ_INVALID = 0, 1, 2, 3, 4, 5, 6
+READ_STATUS_NAMES = ["SERVED", "BEHIND", "GAPPED", "NO_QUORUM", "DEPOSED", "NONE", "INVALID"]
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -397,6 +415,10 @@ def load_library(path: str | None = None):
         "raft_engine_restart": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
         "raft_engine_restart_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
         "raft_engine_restart_random": (C.c_int, [eng, I64, I64, C.c_uint32, I32, I32, P(raft_restart_info)]),
+        "raft_read_begin_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
+        "raft_read_begin_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
+        "raft_read_serve_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_read_serve_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -454,6 +476,7 @@ EXPORTED_SYMBOLS = [
     "raft_engine_sm_configure", "raft_engine_sm_apply", "raft_engine_sm_read", "raft_engine_sm_write",
     "raft_engine_sm_get", "raft_engine_sm_check",
     "raft_engine_restart", "raft_engine_restart_dev", "raft_engine_restart_random",
+    "raft_read_begin_batch", "raft_read_begin_batch_dev", "raft_read_serve_batch", "raft_read_serve_batch_dev",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

@@ -2,8 +2,8 @@
 // (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
 // batches, include/raft_engine.h raft_*_batch*), raft_apply.hip (the
 // committed-entry drain), raft_client.hip (the leader directory, routed
-// proposals and tickets), raft_sm.hip (the replicated state machine) and
-// raft_fault.hip (replica restart) share -- the engine object, the HBM indexing helpers, a replica's quad load /
+// proposals and tickets), raft_sm.hip (the replicated state machine),
+// raft_fault.hip (replica restart) and raft_read.hip (linearizable reads) share -- the engine object, the HBM indexing helpers, a replica's quad load /
 // store, the leader lookup and the error / staging entry points.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -118,6 +118,31 @@ __device__ __forceinline__ Lead find_leader(const DevParams& p, int64_t g) {
             l.r = r;
             l.term = q[r].x;
             ++l.n;
+        }
+    }
+    return l;
+}
+
+// The group's newest leader, the one a linearizable read asks (raft_read.hip):
+// of the replicas whose role is LEADER the one with the highest currentTerm,
+// the lowest index among equals.  Not find_leader's rule: a deposed leader
+// keeps its role until it hears of the new term, and at a lower index it would
+// shadow its successor.  The same R loads of quad 0, all in flight at once.
+__device__ __forceinline__ Lead find_newest_leader(const DevParams& p, int64_t g) {
+    const int R = p.R;
+    const int64_t base = g * R;
+    int4 q[RAFT_MAX_R];
+#pragma unroll
+    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
+    Lead l{-1, 0, 0};
+#pragma unroll
+    for (int r = RAFT_MAX_R - 1; r >= 0; --r) {                       // descending: of equal terms the lowest id is taken last
+        if (r < R && q[r].z == RAFT_LEADER) {
+            ++l.n;
+            if (l.r < 0 || q[r].x >= l.term) {
+                l.r = r;
+                l.term = q[r].x;
+            }
         }
     }
     return l;

@@ -407,6 +407,63 @@ class RaftEngine:
                                                                              out_ptr, int(n)),
                                    "raft_engine_resolve_tickets_dev")
 
+    # -- linearizable reads (raft_read_begin_batch*, raft_read_serve_batch*) --------
+    def begin_reads(self, groups) -> np.ndarray:
+        """raft_read_begin_batch: a read ticket per entry of `groups`, as
+        abi.READ_TICKET_DTYPE records (replica: the group's newest leader, term,
+        read_index: its committed prefix, status = abi.READ_ISSUED /
+        READ_TERM_UNCOMMITTED / READ_NO_LEADER / READ_UNKNOWN).  Read-only.
+        RAFT_EWINDOW (some ticket is UNKNOWN) is not raised: ``last_status``
+        carries the code."""
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        if g.ndim != 1:
+            raise ValueError(f"begin_reads: groups {g.shape} must be 1-D")
+        t = np.zeros(g.shape[0], dtype=abi.READ_TICKET_DTYPE)
+        self._client_status(self._lib.raft_read_begin_batch(self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data),
+                                                            g.shape[0]), "raft_read_begin_batch")
+        return t
+
+    def begin_reads_dev(self, group_ptr: int, ticket_ptr: int, n: int, after_stream: int | None = None) -> int:
+        """raft_read_begin_batch_dev: DEVICE pointers to n int64 groups and
+        16-byte tickets (16-byte aligned); returns RAFT_OK or RAFT_EWINDOW."""
+        if ticket_ptr % 16:
+            raise ValueError("begin_reads_dev: the ticket buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_read_begin_batch_dev(self._h, group_ptr, ticket_ptr, int(n)),
+                                   "raft_read_begin_batch_dev")
+
+    def serve_reads(self, groups, tickets, keys, check: bool = True) -> np.ndarray:
+        """raft_read_serve_batch: register keys[m] (its low bits name the
+        slot) of the replica tickets[m] names in groups[m], confirmed against
+        the group's terms, as abi.READ_RESULT_DTYPE records (value, status =
+        abi.READ_SERVED ... READ_INVALID, applied, agree).  Read-only; needs
+        sm_configure.  With check=False RAFT_ERANGE / RAFT_EINVAL (some record
+        is INVALID) are not raised: ``last_status`` carries the code."""
+        g, k = self._client_arrays(groups, keys, "serve_reads")
+        t = np.ascontiguousarray(tickets)
+        if t.dtype != abi.READ_TICKET_DTYPE or t.ndim != 1 or t.shape[0] != g.shape[0]:
+            raise ValueError(f"serve_reads: tickets must be {g.shape[0]} records of abi.READ_TICKET_DTYPE")
+        out = np.zeros(g.shape[0], dtype=abi.READ_RESULT_DTYPE)
+        # an unconfigured machine is RAFT_EINVAL too, and fills nothing: that one always raises
+        allowed = () if check or not self.sm_slots else (abi.RAFT_ERANGE, abi.RAFT_EINVAL)
+        self._client_status(self._lib.raft_read_serve_batch(
+            self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(k.ctypes.data),
+            C.c_void_p(out.ctypes.data), g.shape[0]), "raft_read_serve_batch", allowed)
+        return out
+
+    def serve_reads_dev(self, group_ptr: int, ticket_ptr: int, key_ptr: int, out_ptr: int, n: int,
+                        after_stream: int | None = None, check: bool = True) -> int:
+        """raft_read_serve_batch_dev on DEVICE pointers (tickets and records
+        16-byte aligned); returns the call's code (see serve_reads)."""
+        if ticket_ptr % 16 or out_ptr % 16:
+            raise ValueError("serve_reads_dev: the ticket and record buffers must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        allowed = () if check or not self.sm_slots else (abi.RAFT_ERANGE, abi.RAFT_EINVAL)
+        return self._client_status(self._lib.raft_read_serve_batch_dev(self._h, group_ptr, ticket_ptr, key_ptr, out_ptr,
+                                                                       int(n)), "raft_read_serve_batch_dev", allowed)
+
     # -- the replicated state machine (raft_engine_sm_*) -------------------------
     @property
     def sm_slots(self) -> int:

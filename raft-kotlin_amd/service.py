@@ -18,6 +18,9 @@ argument meaning and error behaviour:
 * ``RaftService.apply_committed`` / ``read`` and ``RaftNode.machine``: the
   replicated state machine on the device -- committed entries applied where
   they are, a register read routed to the leader, a node's head and registers
+* ``RaftService.read_linearizable``: the read a client can trust -- a ReadIndex
+  ticket from the group's newest leader, confirmed against a majority of the
+  group's terms before the register is read
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -241,6 +244,46 @@ class RaftService:
         name = self.commands.name
         return [(name(c), r, a, m) for c, r, a, m in
                 zip(v["value"].tolist(), v["replica"].tolist(), v["applied"].tolist(), v["commit"].tolist())]
+
+    def read_linearizable(self, groups, keys: List[str]) -> List[tuple]:
+        """The read a client can trust: per request (command, status name).
+        One begin (a ReadIndex ticket from each group's newest leader), one
+        serve of the tickets that were ISSUED (the leader confirmed against a
+        majority of the group's terms), and where a leader's machine was BEHIND
+        its read index an apply_committed of those groups alone (one call per
+        run of consecutive group ids) and one more serve of them.  The engine is never stepped.  command is the one last applied
+        to the register keys[m] maps to (named by CommandTable.name) when the
+        status is "SERVED", else None; the other statuses are "BEHIND" (still,
+        after the apply), "GAPPED", "NO_QUORUM", "DEPOSED", or why no ticket was
+        issued: "NO_LEADER", "TERM_UNCOMMITTED", "UNKNOWN" -- the client retries
+        after a step.  ``last_read`` keeps (tickets, records).  Keys as in read:
+        one that was never interned raises KeyError before any device call."""
+        ids = [self.commands.lookup(k) for k in keys]
+        unknown = [k for k, i in zip(keys, ids) if i is None]
+        if unknown:
+            raise KeyError(f"read_linearizable: never submitted, so no register holds it: {unknown[0]!r}")
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        k = np.asarray(ids, dtype=np.uint32)
+        tk = self.engine.begin_reads(g)
+        rec = np.zeros(len(g), dtype=abi.READ_RESULT_DTYPE)
+        rec["status"] = abi.READ_NONE
+        todo = np.nonzero(tk["status"] == abi.READ_ISSUED)[0]
+        for attempt in range(2):
+            if not len(todo):
+                break
+            rec[todo] = self.engine.serve_reads(g[todo], tk[todo], k[todo])
+            todo = todo[rec["status"][todo] == abi.READ_BEHIND]
+            if attempt == 0 and len(todo):
+                # the BEHIND groups only: one apply per run of consecutive group ids
+                ids_ = np.unique(g[todo])
+                cuts = np.nonzero(np.diff(ids_) != 1)[0] + 1
+                for run in np.split(ids_, cuts):
+                    self.apply_committed(int(run[0]), len(run))
+        self.last_read = (tk, rec)
+        name = self.commands.name
+        return [(name(v), "SERVED") if s == abi.READ_SERVED else
+                (None, abi.READ_TICKET_STATUS_NAMES[t] if s == abi.READ_NONE else abi.READ_STATUS_NAMES[s])
+                for v, s, t in zip(rec["value"].tolist(), rec["status"].tolist(), tk["status"].tolist())]
 
     # -- crash and restart: the JVM of a node killed and relaunched (RaftServer.kt:302-310) ---
     def restart(self, groups, replicas, amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
