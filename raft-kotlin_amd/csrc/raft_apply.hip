@@ -31,13 +31,6 @@ using namespace raft;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 static_assert(sizeof(raft_applied_entry) == 24 && sizeof(raft_drain_info) == 32, "record layouts of the C-ABI");
 
 constexpr int HDR_LOST = 0, HDR_REGRESSED = 1;       // unsigned long long words of the staging header
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(BLOCK) void apply_count_kernel(DevParams p, int32_t
         const int64_t idx = sel_idx<R>(s, j);
         const int32_t commit = p.st[fidx(p, RAFT_F_COMMIT, idx)];
         const int32_t last = p.st[fidx(p, RAFT_F_LAST, idx)];
-        const int32_t hi = max(0, min(min(commit, last), p.cap));      // the committed prefix (log_match_kernel's)
+        const int32_t hi = committed_hi(p, commit, last);
         int32_t lo = applied[idx];
         if (p.W != FLAT_W) {                                           // a ring: entries below the window are gone
             const int32_t wl = max(0, p.st[fidx(p, RAFT_F_PHYS, idx)] - p.W);

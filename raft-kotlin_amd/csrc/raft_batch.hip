@@ -25,18 +25,6 @@
 
 namespace {
 
-int fail(int code, const std::string& msg) { return raft_internal_fail(code, msg); }
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess)                                                              \
-            return fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-int grow_dev(raft_engine* e, char** buf, size_t* have, size_t need) { return raft_internal_grow_dev(e, buf, have, need); }
-int grow_host(raft_engine* e, char** buf, size_t* have, size_t need) { return raft_internal_grow_host(e, buf, have, need); }
-
 // ---------------------------------------------------------------------------
 // single-handler batches: one lane per distinct (group, replica), its
 // messages applied in batch order
@@ -407,23 +395,18 @@ void bucket_batch_kernel(DevParams p, uint32_t t, int n, int S, int NB, int ntil
 
 }  // namespace
 
-// rocprim's radix sort takes its merge-sort path up to 2^20 items (one
-// block sort and ~10 merge passes over the whole array, 21 dispatches at 10^6
-// messages); a merge limit of 0 keeps it on the onesweep path (a histogram
-// pass and one pass per 8 key bits).
-using BatchSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                   rocprim::default_config, 0>;
+// (the sort's configuration, SortConfig: raft_engine_impl.h)
 template <class Key>
 static int run_batch_keys(raft_engine* e, int kind, const int64_t* group, const int32_t* dst, const void* req,
                           void* resp, int n, int bits) {
     const int R = e->p.R;
     size_t sort_tmp = 0;
-    HIP_TRY(rocprim::radix_sort_pairs<BatchSortConfig>(nullptr, sort_tmp, (const Key*)nullptr, (Key*)nullptr,
+    HIP_TRY(rocprim::radix_sort_pairs<SortConfig>(nullptr, sort_tmp, (const Key*)nullptr, (Key*)nullptr,
                                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u,
                                                        (unsigned)bits, e->stream));
     const size_t b_keys = al256((size_t)n * sizeof(Key)), b_ord = al256((size_t)n * 4);
     const size_t sz0 = e->bst_bytes;
-    if (int rc = grow_dev(e, &e->bst, &e->bst_bytes, BST_HEAD + 2 * b_keys + 2 * b_ord + al256(sort_tmp) + 256))
+    if (int rc = raft_internal_grow_dev(e, &e->bst, &e->bst_bytes, BST_HEAD + 2 * b_keys + 2 * b_ord + al256(sort_tmp) + 256))
         return rc;
     if (e->bst_bytes != sz0) HIP_TRY(hipMemsetAsync(e->bst, 0, BST_HEAD, e->stream));   // (the bucketed path's words)
     char* b = e->bst + BST_HEAD;
@@ -436,7 +419,7 @@ static int run_batch_keys(raft_engine* e, int kind, const int64_t* group, const 
     HIP_TRY(hipMemsetAsync(flags, 0, 8, e->stream));
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
     batch_keys_kernel<Key><<<grid, BLOCK, 0, e->stream>>>(group, dst, n, e->p.G, R, k_in, o_in, flags);
-    HIP_TRY(rocprim::radix_sort_pairs<BatchSortConfig>(tmp, sort_tmp, k_in, k_out, o_in, o_out, n, 0u, (unsigned)bits,
+    HIP_TRY(rocprim::radix_sort_pairs<SortConfig>(tmp, sort_tmp, k_in, k_out, o_in, o_out, n, 0u, (unsigned)bits,
                                                        e->stream));
     using BK = void (*)(DevParams, uint32_t, int, const Key*, const uint32_t*, const void*, void*, unsigned int*);
     const bool tb = e->p.mode == RAFT_MODE_TEXTBOOK;
@@ -476,8 +459,8 @@ static int run_batch_buckets(raft_engine* e, int kind, const int64_t* group, con
     while ((uint64_t)(NB - 1) >> bbits) ++bbits;
     const int ntile = (int)ntile64;
     const size_t b_t = al256((size_t)ntile * TILE * 8), b_s = al256((size_t)NB * ntile * 8);
-    const size_t sz0 = e->bst_bytes;                                    // grow_dev reallocates only to grow
-    if (int rc = grow_dev(e, &e->bst, &e->bst_bytes, BST_HEAD + b_t + b_s)) return rc;
+    const size_t sz0 = e->bst_bytes;                                    // the staging reallocates only to grow
+    if (int rc = raft_internal_grow_dev(e, &e->bst, &e->bst_bytes, BST_HEAD + b_t + b_s)) return rc;
     char* b = e->bst + BST_HEAD;
     uint2* tiles = (uint2*)b; b += b_t;
     uint2* seg = (uint2*)b; b += b_s;
@@ -534,26 +517,18 @@ static int run_batch_dev(raft_engine* e, int kind, const int64_t* group, const i
     int bits = 1;
     while (bits < 64 && (nkeys - 1) >> bits) ++bits;
     if (e->batch_path == RAFT_BATCH_PATH_BUCKETED && bits > 32)
-        return fail(RAFT_EINVAL, "the bucketed batch path needs G * R <= 2^32");
+        return raft_internal_fail(RAFT_EINVAL, "the bucketed batch path needs G * R <= 2^32");
     const int rc = e->batch_path != RAFT_BATCH_PATH_SORTED && bits <= 32
                        ? run_batch_buckets(e, kind, group, dst, req, resp, n, nkeys)
                    : bits <= 32 ? run_batch_keys<uint32_t>(e, kind, group, dst, req, resp, n, bits)
                                 : run_batch_keys<uint64_t>(e, kind, group, dst, req, resp, n, bits);
     if (rc) return rc;
-    if (e->bflags_host[0]) return fail(RAFT_ERANGE, "a message's group or replica index is outside the engine; "
-                                                    "nothing was applied");
+    if (e->bflags_host[0])
+        return raft_internal_fail(RAFT_ERANGE, "a message's group or replica index is outside the engine; nothing was applied");
     if (e->bflags_host[1])
-        return fail(RAFT_EWINDOW, std::to_string(e->bflags_host[1]) + " log accesses below the retained log_window: "
-                                  "the batch's results are not the reference's");
-    return RAFT_OK;
-}
-
-static int check_batch_args(raft_engine* e, int64_t n, const void* group, const void* dst, const void* req,
-                            size_t resp_sz, const void* resp) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
-    if (n < 0) return fail(RAFT_EINVAL, "negative batch");
-    if (n > 0x7FFFFFFF) return fail(RAFT_EINVAL, "batch larger than 2^31 - 1 messages");
-    if (n > 0 && (!group || !dst || !req || (resp_sz && !resp))) return fail(RAFT_EINVAL, "null buffer");
+        return raft_internal_fail(RAFT_EWINDOW, std::to_string(e->bflags_host[1]) +
+                                                    " log accesses below the retained log_window: the batch's "
+                                                    "results are not the reference's");
     return RAFT_OK;
 }
 
@@ -595,19 +570,19 @@ static void batch_memcpy(void* d, const void* s, size_t n) {
 // engine-owned pinned staging (a multi-threaded memcpy per array).
 static int run_batch(raft_engine* e, int kind, const int64_t* group, const int32_t* dst, const void* req,
                      size_t req_sz, void* resp, size_t resp_sz, int64_t n) {
-    if (int rc = check_batch_args(e, n, group, dst, req, resp_sz, resp)) return rc;
+    if (int rc = check_args(e, n, !group || !dst || !req || (resp_sz && !resp))) return rc;
     if (n == 0) return RAFT_OK;
     HIP_TRY(hipSetDevice(e->device));
     const size_t b_g = al256((size_t)n * 8), b_d = al256((size_t)n * 4), b_q = al256((size_t)n * req_sz);
     const size_t b_s = al256((size_t)n * resp_sz), in_b = b_g + b_d + b_q;
-    if (int rc = grow_dev(e, &e->bio, &e->bio_bytes, in_b + b_s)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->bio, &e->bio_bytes, in_b + b_s)) return rc;
     const bool pinned = host_pinned(group) && host_pinned(dst) && host_pinned(req) && (!resp_sz || host_pinned(resp));
     if (pinned) {
         HIP_TRY(hipMemcpyAsync(e->bio, group, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(e->bio + b_g, dst, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(e->bio + b_g + b_d, req, (size_t)n * req_sz, hipMemcpyHostToDevice, e->stream));
     } else {
-        if (int rc = grow_host(e, &e->hst, &e->hst_bytes, in_b + b_s)) return rc;
+        if (int rc = raft_internal_grow_host(e, &e->hst, &e->hst_bytes, in_b + b_s)) return rc;
         batch_memcpy(e->hst, group, (size_t)n * 8);
         batch_memcpy(e->hst + b_g, dst, (size_t)n * 4);
         batch_memcpy(e->hst + b_g + b_d, req, (size_t)n * req_sz);
@@ -627,7 +602,7 @@ static int run_batch(raft_engine* e, int kind, const int64_t* group, const int32
 
 static int run_batch_on_device(raft_engine* e, int kind, const int64_t* group, const int32_t* dst, const void* req,
                                size_t resp_sz, void* resp, int64_t n) {
-    if (int rc = check_batch_args(e, n, group, dst, req, resp_sz, resp)) return rc;
+    if (int rc = check_args(e, n, !group || !dst || !req || (resp_sz && !resp))) return rc;
     if (n == 0) return RAFT_OK;
     HIP_TRY(hipSetDevice(e->device));
     return run_batch_dev(e, kind, group, dst, req, resp, n);
@@ -679,8 +654,8 @@ int raft_append_command_batch_dev(raft_engine* e, const int64_t* group, const in
 
 
 int raft_engine_set_batch_path(raft_engine* e, int32_t path) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
-    if (path < RAFT_BATCH_PATH_AUTO || path > RAFT_BATCH_PATH_BUCKETED) return fail(RAFT_EINVAL, "unknown batch path");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (path < RAFT_BATCH_PATH_AUTO || path > RAFT_BATCH_PATH_BUCKETED) return raft_internal_fail(RAFT_EINVAL, "unknown batch path");
     e->batch_path = path;
     return RAFT_OK;
 }

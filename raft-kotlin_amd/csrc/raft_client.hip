@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include <cstring>
 #include <string>
 
 #include "raft_engine_impl.h"
@@ -32,19 +31,13 @@ using namespace raft;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 static_assert(sizeof(raft_leader_info) == 16 && sizeof(raft_ticket) == 16 && sizeof(raft_ticket_state) == 16,
               "record layouts of the C-ABI");
 
-// status words of a call (device; copied to the engine's page-locked words)
+// status words of a call (DevWords, raft_engine_impl.h: one stripe), at the head of cli
 enum { CW_RANGE = 0, CW_MISS = 1, CW_INVAL = 2, CW_UNKNOWN = 3, CW_WORDS = 4 };
 constexpr size_t CW_BYTES = 256;
+using Status = DevWords<unsigned int, 1, CW_WORDS, CW_WORDS, false>;
 
 // (the group's leader, find_leader: raft_engine_impl.h)
 __global__ __launch_bounds__(BLOCK) void leaders_kernel(DevParams p, int64_t g0, int64_t n, int4* __restrict__ out) {
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(DevParams p, const int64
         } else if (i < last) {
             const uint2 en = *log_of(p, idx).at<true>(i);
             if ((int32_t)en.x == tk.z && en.y == c) {
-                const int32_t hi = max(0, min(min(commit, last), p.cap));   // the committed prefix (the drain's)
+                const int32_t hi = committed_hi(p, commit, last);
                 v = 1u | (i < hi ? 1u << 8 : 0u) | (r == tk.x ? 1u << 24 : 0u);
             }
         }
@@ -178,27 +171,7 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(DevParams p, const int64
     out[m] = make_int4(st, holders, com, unk);                          // raft_ticket_state
 }
 
-int check_args(raft_engine* e, int64_t n, bool any_null) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (n < 0) return raft_internal_fail(RAFT_EINVAL, "negative batch");
-    if (n > 0x7FFFFFFF) return raft_internal_fail(RAFT_EINVAL, "batch larger than 2^31 - 1 messages");
-    if (n > 0 && any_null) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    return RAFT_OK;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-// the status words of a finished call, in the engine's page-locked words
-int fetch_flags(raft_engine* e, const unsigned int* flags) {
-    HIP_TRY(hipMemcpyAsync(e->bflags_host, flags, CW_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
-}
-
-// as raft_batch.hip's: a merge limit of 0 keeps rocprim on the onesweep path
-using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                              rocprim::default_config, 0>;
-
+// (the sort's configuration, SortConfig: raft_engine_impl.h)
 int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int n) {
     e->fork_needed = true;
     raft_internal_ensure_cache(e);                  // append_command reads and writes the HBM tail cache
@@ -210,27 +183,27 @@ int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_
                                                   e->stream));
     const size_t b_n = al256((size_t)n * 4);
     if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, CW_BYTES + 4 * b_n + al256(sort_tmp))) return rc;
-    unsigned int* flags = (unsigned int*)e->cli;
+    Status st;
     uint32_t* k_in = (uint32_t*)(e->cli + CW_BYTES);
     uint32_t* k_out = (uint32_t*)(e->cli + CW_BYTES + b_n);
     uint32_t* o_in = (uint32_t*)(e->cli + CW_BYTES + 2 * b_n);
     uint32_t* o_out = (uint32_t*)(e->cli + CW_BYTES + 3 * b_n);
     void* tmp = e->cli + CW_BYTES + 4 * b_n;
-    HIP_TRY(hipMemsetAsync(flags, 0, CW_WORDS * 4, e->stream));
+    if (int rc = st.zero(e, e->cli)) return rc;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    propose_keys_kernel<<<grid, BLOCK, 0, e->stream>>>(group, n, e->p.G, k_in, o_in, flags);
+    propose_keys_kernel<<<grid, BLOCK, 0, e->stream>>>(group, n, e->p.G, k_in, o_in, st.dev);
     HIP_TRY(rocprim::radix_sort_pairs<SortConfig>(tmp, sort_tmp, k_in, k_out, o_in, o_out, n, 0u, (unsigned)bits,
                                                   e->stream));
     if (e->p.mode == RAFT_MODE_TEXTBOOK)
-        propose_kernel<true><<<grid, BLOCK, 0, e->stream>>>(e->dp, n, k_out, o_out, cmd, (int4*)ticket, flags);
+        propose_kernel<true><<<grid, BLOCK, 0, e->stream>>>(e->dp, n, k_out, o_out, cmd, (int4*)ticket, st.dev);
     else
-        propose_kernel<false><<<grid, BLOCK, 0, e->stream>>>(e->dp, n, k_out, o_out, cmd, (int4*)ticket, flags);
+        propose_kernel<false><<<grid, BLOCK, 0, e->stream>>>(e->dp, n, k_out, o_out, cmd, (int4*)ticket, st.dev);
     HIP_TRY(hipGetLastError());
-    if (int rc = fetch_flags(e, flags)) return rc;
-    if (e->bflags_host[CW_RANGE])
+    if (int rc = st.fetch(e)) return rc;
+    if (st.w[CW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a proposal's group is outside the engine; nothing was applied");
-    if (e->bflags_host[CW_MISS])
-        return raft_internal_fail(RAFT_EWINDOW, std::to_string(e->bflags_host[CW_MISS]) +
+    if (st.w[CW_MISS])
+        return raft_internal_fail(RAFT_EWINDOW, std::to_string(st.w[CW_MISS]) +
                                                     " log accesses below the retained log_window: the batch's "
                                                     "results are not the reference's");
     return RAFT_OK;
@@ -240,46 +213,18 @@ int resolve_dev(raft_engine* e, const int64_t* group, const raft_ticket* ticket,
                 raft_ticket_state* out, int64_t n) {
     e->fork_needed = true;                          // later step launches wait for these reads of the state and logs
     if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, CW_BYTES)) return rc;
-    unsigned int* flags = (unsigned int*)e->cli;
-    HIP_TRY(hipMemsetAsync(flags, 0, CW_WORDS * 4, e->stream));
+    Status st;
+    if (int rc = st.zero(e, e->cli)) return rc;
     const unsigned grid = (unsigned)((n * RAFT_MAX_R + BLOCK - 1) / BLOCK);
-    resolve_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, group, (const int4*)ticket, cmd, (int4*)out, n, flags);
+    resolve_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, group, (const int4*)ticket, cmd, (int4*)out, n, st.dev);
     HIP_TRY(hipGetLastError());
-    if (int rc = fetch_flags(e, flags)) return rc;
-    if (e->bflags_host[CW_RANGE])
+    if (int rc = st.fetch(e)) return rc;
+    if (st.w[CW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a ticket's group is outside the engine (its record is INVALID)");
-    if (e->bflags_host[CW_INVAL])
+    if (st.w[CW_INVAL])
         return raft_internal_fail(RAFT_EINVAL, "a ticket's replica or index is outside the engine (its record is INVALID)");
-    if (e->bflags_host[CW_UNKNOWN])
+    if (st.w[CW_UNKNOWN])
         return raft_internal_fail(RAFT_EWINDOW, "a ticket's slot is below a replica's log_window (its record is UNKNOWN)");
-    return RAFT_OK;
-}
-
-// A host call's arrays: copied into the engine's page-locked staging (hst),
-// moved with one DMA to their device copies (cio); the results come back the
-// same way.  Layout of both: the inputs, 256-byte aligned each, then the output.
-struct Staged {
-    size_t off[4];
-    size_t in_bytes, out_off, out_bytes;
-};
-int stage_in(raft_engine* e, const void* const* src, const size_t* bytes, int k, size_t out_bytes, Staged& s) {
-    size_t at = 0;
-    for (int i = 0; i < k; ++i) {
-        s.off[i] = at;
-        at += al256(bytes[i]);
-    }
-    s.in_bytes = s.out_off = at;
-    s.out_bytes = out_bytes;
-    if (int rc = raft_internal_grow_dev(e, &e->cio, &e->cio_bytes, at + al256(out_bytes))) return rc;
-    if (int rc = raft_internal_grow_host(e, &e->hst, &e->hst_bytes, at + al256(out_bytes))) return rc;
-    for (int i = 0; i < k; ++i) std::memcpy(e->hst + s.off[i], src[i], bytes[i]);
-    HIP_TRY(hipMemcpyAsync(e->cio, e->hst, s.in_bytes, hipMemcpyHostToDevice, e->stream));
-    return RAFT_OK;
-}
-int stage_out(raft_engine* e, const Staged& s, void* dst) {
-    HIP_TRY(hipMemcpyAsync(e->hst + s.out_off, e->cio + s.out_off, s.out_bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    std::memcpy(dst, e->hst + s.out_off, s.out_bytes);
     return RAFT_OK;
 }
 
@@ -288,8 +233,7 @@ int stage_out(raft_engine* e, const Staged& s, void* dst) {
 extern "C" {
 
 int raft_engine_read_leaders(raft_engine* e, int64_t g0, int64_t n, raft_leader_info* out_host) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (g0 < 0 || n < 0 || g0 + n > e->p.G) return raft_internal_fail(RAFT_ERANGE, "group range outside the engine");
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
     if (!out_host) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));

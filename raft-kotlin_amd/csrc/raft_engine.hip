@@ -25,18 +25,6 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess)                                                              \
-            return fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 #ifdef RAFT_PROFILE_PHASES
 __device__ unsigned long long g_phase_cycles[PH_N];   // diagnostic builds only
 #endif
@@ -1049,8 +1037,9 @@ static int launch_geo(raft_engine* e, StepKernel kern, int k, int epoch, LaunchG
         // workgroup's m = ceil(n / nb) chunks
         const int kp_ = epoch > 0 ? std::min(k, epoch) : k;                // a plan spans one epoch
         if (bal && (uint64_t)STEP_WAVES * (uint64_t)((n + geo.nb[q] - 1) / geo.nb[q]) * (uint64_t)kp_ >= (1ull << 32))
-            return fail(RAFT_EINVAL, "balanced launch too long for its workgroups (4 * chunks per workgroup * "
-                                     "steps_per_launch >= 2^32): raise schedule_workgroups or lower steps_per_launch");
+            return raft_internal_fail(RAFT_EINVAL,
+                                      "balanced launch too long for its workgroups (4 * chunks per workgroup * "
+                                      "steps_per_launch >= 2^32): raise schedule_workgroups or lower steps_per_launch");
         geo.col0[q] = geo.stride;
         geo.stride += geo.nb[q];
         geo.balanced += bal;
@@ -1106,7 +1095,10 @@ template <int R> struct DigestL {
 };
 
 // raft_wire.cpp reports its errors through raft_last_error() too
-int raft_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+int raft_internal_fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
 void raft_internal_ensure_cache(raft_engine* e) {
     if (e->cache_valid) return;
     rebuild_cache_kernel<<<(unsigned)((e->dp.GR + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(e->dp);
@@ -1159,34 +1151,34 @@ void raft_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t o
 }
 
 int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
-    if (!p || !out) return fail(RAFT_EINVAL, "null argument");
+    if (!p || !out) return raft_internal_fail(RAFT_EINVAL, "null argument");
     *out = nullptr;
-    if (p->R < 1 || p->R > RAFT_MAX_R) return fail(RAFT_EINVAL, "R must be in 1..8");
-    if (p->G < 1 || p->G > (int64_t)0x7FFFFFFF) return fail(RAFT_EINVAL, "G out of range");
-    if (p->g0 < 0 || p->g0 + p->G > (int64_t)0x100000000ll) return fail(RAFT_EINVAL, "g0 + G exceeds 2^32");
-    if (p->log_cap < 1) return fail(RAFT_EINVAL, "log_cap must be >= 1");
+    if (p->R < 1 || p->R > RAFT_MAX_R) return raft_internal_fail(RAFT_EINVAL, "R must be in 1..8");
+    if (p->G < 1 || p->G > (int64_t)0x7FFFFFFF) return raft_internal_fail(RAFT_EINVAL, "G out of range");
+    if (p->g0 < 0 || p->g0 + p->G > (int64_t)0x100000000ll) return raft_internal_fail(RAFT_EINVAL, "g0 + G exceeds 2^32");
+    if (p->log_cap < 1) return raft_internal_fail(RAFT_EINVAL, "log_cap must be >= 1");
     if (p->steps_per_launch < 0 || p->steps_per_launch > RAFT_MAX_STEPS_PER_LAUNCH)
-        return fail(RAFT_EINVAL, "steps_per_launch must be in 0..RAFT_MAX_STEPS_PER_LAUNCH");
+        return raft_internal_fail(RAFT_EINVAL, "steps_per_launch must be in 0..RAFT_MAX_STEPS_PER_LAUNCH");
     if (p->heartbeat_ms <= 0 || p->election_min_ms > p->election_max_ms || p->backoff_min_ms > p->backoff_max_ms)
-        return fail(RAFT_EINVAL, "bad timer constants");
+        return raft_internal_fail(RAFT_EINVAL, "bad timer constants");
     if (p->mode != RAFT_MODE_REFERENCE && p->mode != RAFT_MODE_TEXTBOOK)
-        return fail(RAFT_EINVAL, "mode must be RAFT_MODE_REFERENCE or RAFT_MODE_TEXTBOOK");
+        return raft_internal_fail(RAFT_EINVAL, "mode must be RAFT_MODE_REFERENCE or RAFT_MODE_TEXTBOOK");
     if (p->log_window < 0 || (p->log_window & (p->log_window - 1)) || p->log_window > p->log_cap)
-        return fail(RAFT_EINVAL, "log_window must be 0 or a power of two <= log_cap");
+        return raft_internal_fail(RAFT_EINVAL, "log_window must be 0 or a power of two <= log_cap");
     if (p->ae_max_entries < 0 || p->ae_max_entries > RAFT_MAX_AE_ENTRIES ||
         (p->mode != RAFT_MODE_TEXTBOOK && p->ae_max_entries > 1))
-        return fail(RAFT_EINVAL, "ae_max_entries must be 0..RAFT_MAX_AE_ENTRIES, and 0 or 1 in reference mode");
+        return raft_internal_fail(RAFT_EINVAL, "ae_max_entries must be 0..RAFT_MAX_AE_ENTRIES, and 0 or 1 in reference mode");
     if (p->subranges < 0 || p->subranges > RAFT_MAX_SUBRANGES)
-        return fail(RAFT_EINVAL, "subranges must be 0..RAFT_MAX_SUBRANGES");
+        return raft_internal_fail(RAFT_EINVAL, "subranges must be 0..RAFT_MAX_SUBRANGES");
     if (p->schedule < RAFT_SCHED_AUTO || p->schedule > RAFT_SCHED_BALANCED || p->schedule_workgroups < 0)
-        return fail(RAFT_EINVAL, "schedule must be a RAFT_SCHED_* value and schedule_workgroups >= 0");
+        return raft_internal_fail(RAFT_EINVAL, "schedule must be a RAFT_SCHED_* value and schedule_workgroups >= 0");
     if (p->kernel != RAFT_KERNEL_AUTO && p->kernel != RAFT_KERNEL_GENERAL)
-        return fail(RAFT_EINVAL, "kernel must be RAFT_KERNEL_AUTO or RAFT_KERNEL_GENERAL");
+        return raft_internal_fail(RAFT_EINVAL, "kernel must be RAFT_KERNEL_AUTO or RAFT_KERNEL_GENERAL");
     if ((p->log_window ? p->log_window : p->log_cap) >= (1 << 23))
-        return fail(RAFT_EINVAL, "log slots per replica (log_window, else log_cap) must be < 2^23");
+        return raft_internal_fail(RAFT_EINVAL, "log slots per replica (log_window, else log_cap) must be < 2^23");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RAFT_ENODEV, "no HIP device");
-    if (device < 0 || device >= ndev) return fail(RAFT_EINVAL, "bad device index");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return raft_internal_fail(RAFT_ENODEV, "no HIP device");
+    if (device < 0 || device >= ndev) return raft_internal_fail(RAFT_EINVAL, "bad device index");
     HIP_TRY(hipSetDevice(device));
 
     raft_engine* e = new raft_engine();
@@ -1273,12 +1265,12 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     const size_t acc_b = (size_t)RAFT_MAX_STEPS_PER_LAUNCH * NC * 8;
     e->bytes = al(st_b) + al(spill_b) + al(gx_b) + 2 * al(part_b) + al(cnt_b) + al(acc_b) + al(log_b);
     hipError_t err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (err != hipSuccess) { delete e; return fail(RAFT_EDEVICE, "hipStreamCreate failed"); }
+    if (err != hipSuccess) { delete e; return raft_internal_fail(RAFT_EDEVICE, "hipStreamCreate failed"); }
     err = hipMalloc(&e->base, e->bytes);
     if (err != hipSuccess) {
         (void)hipStreamDestroy(e->stream);
         delete e;
-        return fail(RAFT_ENOMEM, "hipMalloc of " + std::to_string(e->bytes) + " bytes failed");
+        return raft_internal_fail(RAFT_ENOMEM, "hipMalloc of " + std::to_string(e->bytes) + " bytes failed");
     }
     // lastApplied: an allocation of its own, outside the state the step kernel, the export and the digest see
     e->applied_bytes = al((size_t)G * R * 4);
@@ -1288,7 +1280,7 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
         (void)hipFree(e->base);
         (void)hipStreamDestroy(e->stream);
         delete e;
-        return fail(RAFT_ENOMEM, "hipMalloc of lastApplied failed");
+        return raft_internal_fail(RAFT_ENOMEM, "hipMalloc of lastApplied failed");
     }
     char* b = (char*)e->base;
     d.st = (int32_t*)b; b += al(st_b);
@@ -1310,7 +1302,7 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     if (err != hipSuccess) {
         raft_engine_destroy(e);
         *out = nullptr;
-        return fail(RAFT_ENOMEM, "hipHostMalloc of the batch status flags failed");
+        return raft_internal_fail(RAFT_ENOMEM, "hipHostMalloc of the batch status flags failed");
     }
     e->part_only = step_net(d, *p, p->R, d.churn_thr32 != 0) == NET_PART;
     if (int rc = raft_engine_set_subranges(e, p->subranges)) {
@@ -1328,7 +1320,7 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
         (void)hipStreamDestroy(e->stream);
         delete e;
         *out = nullptr;
-        return fail(RAFT_EDEVICE, std::string("init kernel: ") + hipGetErrorString(err));
+        return raft_internal_fail(RAFT_EDEVICE, std::string("init kernel: ") + hipGetErrorString(err));
     }
     return RAFT_OK;
 }
@@ -1416,7 +1408,6 @@ int raft_engine_destroy(raft_engine* e) {
 // Grow the timing-event pool to hold `pairs` more launches.  Called when
 // timing is switched on, so a timed region never creates events (64
 // hipEventCreate calls cost ~0.1 ms of host time, 7 % of a 20-step run).
-static int grow_dev(raft_engine* e, char** buf, size_t* have, size_t need);
 static int reserve_events(raft_engine* e, size_t pairs) {
     while (e->ev_used + 2 * pairs > e->ev.size()) {
         hipEvent_t x;
@@ -1427,7 +1418,7 @@ static int reserve_events(raft_engine* e, size_t pairs) {
 }
 
 int raft_engine_step_async(raft_engine* e, int32_t n_steps, int64_t* counters_dev) {
-    if (!e || n_steps < 0) return fail(RAFT_EINVAL, "bad argument");
+    if (!e || n_steps < 0) return raft_internal_fail(RAFT_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(e->device));
     if (n_steps > 0) raft_internal_ensure_cache(e);
     // One sub-range: every launch and its counter reduction on the engine
@@ -1468,7 +1459,7 @@ int raft_engine_step_async(raft_engine* e, int32_t n_steps, int64_t* counters_de
         }
         if (epochs) {
             const size_t need = (size_t)k * NCW * (size_t)geo.stride * 4;
-            if (int rc = grow_dev(e, (char**)&e->hpart, &e->hpart_bytes, need)) return rc;
+            if (int rc = raft_internal_grow_dev(e, (char**)&e->hpart, &e->hpart_bytes, need)) return rc;
             part = e->hpart;
         } else {
             k = std::min(k, LDS_MAX_STEPS);
@@ -1522,19 +1513,20 @@ int raft_engine_step_async(raft_engine* e, int32_t n_steps, int64_t* counters_de
 static int check_device_status(raft_engine* e) {
     const uint32_t s = __atomic_load_n(&e->bflags_host[8], __ATOMIC_ACQUIRE);
     if (s & RAFT_DEV_WAIT_TIMEOUT)
-        return fail(RAFT_EDEVICE, "a balanced-schedule wave timed out waiting for the previous wave's head piece: "
+        return raft_internal_fail(RAFT_EDEVICE,
+                                  "a balanced-schedule wave timed out waiting for the previous wave's head piece: "
                                   "the engine's state is not the reference's (raft_engine_reset clears this)");
     return RAFT_OK;
 }
 
 int raft_engine_sync(raft_engine* e) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     HIP_TRY(hipStreamSynchronize(e->stream));
     return check_device_status(e);
 }
 
 int raft_engine_step(raft_engine* e, int32_t n_steps, int64_t* counters_host) {
-    if (!e || n_steps < 0) return fail(RAFT_EINVAL, "bad argument");
+    if (!e || n_steps < 0) return raft_internal_fail(RAFT_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(e->device));
     for (int32_t done = 0; done < n_steps;) {
         const int k = std::min<int32_t>(e->K, n_steps - done);
@@ -1553,7 +1545,7 @@ int raft_engine_step(raft_engine* e, int32_t n_steps, int64_t* counters_host) {
 void* raft_engine_stream(raft_engine* e) { return e ? (void*)e->stream : nullptr; }
 
 int raft_engine_set_kernel_timing(raft_engine* e, int enable) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     e->timing = enable != 0;
     if (e->timing) {
         HIP_TRY(hipSetDevice(e->device));
@@ -1563,7 +1555,7 @@ int raft_engine_set_kernel_timing(raft_engine* e, int enable) {
 }
 
 int raft_engine_kernel_time(raft_engine* e, double* total_ms, int64_t* launches) {
-    if (!e || !total_ms || !launches) return fail(RAFT_EINVAL, "null argument");
+    if (!e || !total_ms || !launches) return raft_internal_fail(RAFT_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     // intervals relative to the first launch's start, merged: the time during
@@ -1599,8 +1591,8 @@ int raft_engine_kernel_time(raft_engine* e, double* total_ms, int64_t* launches)
     return check_device_status(e);
 }
 int raft_engine_timed_span(raft_engine* e, void* end_event, double* ms) {
-    if (!e || !end_event || !ms) return fail(RAFT_EINVAL, "null argument");
-    if (e->ev_used < 2) return fail(RAFT_EINVAL, "no timed launch since kernel timing was switched on");
+    if (!e || !end_event || !ms) return raft_internal_fail(RAFT_EINVAL, "null argument");
+    if (e->ev_used < 2) return raft_internal_fail(RAFT_EINVAL, "no timed launch since kernel timing was switched on");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipEventSynchronize((hipEvent_t)end_event));
     // from the earliest launch start (a sub-range can start a launch ahead of
@@ -1617,8 +1609,8 @@ int raft_engine_timed_span(raft_engine* e, void* end_event, double* ms) {
 }
 int64_t raft_engine_step_index(raft_engine* e) { return e ? (int64_t)e->t : -1; }
 int raft_engine_set_steps_per_launch(raft_engine* e, int32_t k) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
-    if (k < 0 || k > RAFT_MAX_STEPS_PER_LAUNCH) return fail(RAFT_EINVAL, "steps_per_launch out of range");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (k < 0 || k > RAFT_MAX_STEPS_PER_LAUNCH) return raft_internal_fail(RAFT_EINVAL, "steps_per_launch out of range");
     e->K = k > 0 ? k : 1;
     return RAFT_OK;
 }
@@ -1635,7 +1627,7 @@ int raft_engine_set_steps_per_launch(raft_engine* e, int32_t k) {
 // not balance) and 23 % above one range (profiles/r4_k).
 static int auto_subranges(const raft_engine* e) { return e->part_only ? 3 : 1; }
 int raft_engine_wait_stream(raft_engine* e, void* stream) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     HIP_TRY(hipSetDevice(e->device));
     if (!e->ev_wait) HIP_TRY(hipEventCreateWithFlags(&e->ev_wait, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(e->ev_wait, (hipStream_t)stream));
@@ -1644,14 +1636,14 @@ int raft_engine_wait_stream(raft_engine* e, void* stream) {
     return RAFT_OK;
 }
 int raft_engine_set_kernel(raft_engine* e, int32_t kernel) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     if (kernel != RAFT_KERNEL_AUTO && kernel != RAFT_KERNEL_GENERAL)
-        return fail(RAFT_EINVAL, "kernel must be RAFT_KERNEL_AUTO or RAFT_KERNEL_GENERAL");
+        return raft_internal_fail(RAFT_EINVAL, "kernel must be RAFT_KERNEL_AUTO or RAFT_KERNEL_GENERAL");
     e->p.kernel = kernel;
     return RAFT_OK;
 }
 int raft_engine_reset(raft_engine* e) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (int q = 0; q < e->nsub && e->nsub > 1; ++q) HIP_TRY(hipStreamSynchronize(e->sub_stream[q]));
@@ -1668,13 +1660,13 @@ int raft_engine_reset(raft_engine* e) {
     return RAFT_OK;
 }
 int raft_engine_kernel_info(raft_engine* e, raft_kernel_info* out) {
-    if (!e || !out) return fail(RAFT_EINVAL, "null argument");
+    if (!e || !out) return raft_internal_fail(RAFT_EINVAL, "null argument");
     *out = e->last;
     return RAFT_OK;
 }
 int raft_engine_set_subranges(raft_engine* e, int32_t n) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
-    if (n < 0 || n > RAFT_MAX_SUBRANGES) return fail(RAFT_EINVAL, "subranges must be 0..RAFT_MAX_SUBRANGES");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (n < 0 || n > RAFT_MAX_SUBRANGES) return raft_internal_fail(RAFT_EINVAL, "subranges must be 0..RAFT_MAX_SUBRANGES");
     if (n == 0) n = auto_subranges(e);
     n = std::min(n, e->nblocks);
     HIP_TRY(hipSetDevice(e->device));
@@ -1694,7 +1686,7 @@ int raft_engine_set_subranges(raft_engine* e, int32_t n) {
 }
 int32_t raft_engine_subranges(raft_engine* e) { return e ? e->nsub : -1; }
 int raft_engine_set_step_index(raft_engine* e, int64_t t) {
-    if (!e || t < 0 || t > (int64_t)0xFFFFFFFFll) return fail(RAFT_EINVAL, "bad step index");
+    if (!e || t < 0 || t > (int64_t)0xFFFFFFFFll) return raft_internal_fail(RAFT_EINVAL, "bad step index");
     e->t = (uint64_t)t;
     return RAFT_OK;
 }
@@ -1704,7 +1696,7 @@ int64_t raft_engine_device_bytes(raft_engine* e) {
              : -1;
 }
 int raft_engine_trim_staging(raft_engine* e) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->bst) HIP_TRY(hipFree(e->bst));
@@ -1723,7 +1715,7 @@ int raft_engine_trim_staging(raft_engine* e) {
 
 // Grow-only engine staging (the batch path, the state / log / digest accessors) (no allocation, and so no
 // device-wide hipFree synchronisation, once a batch size has been seen).
-static int grow_dev(raft_engine* e, char** buf, size_t* have, size_t need) {
+int raft_internal_grow_dev(raft_engine* e, char** buf, size_t* have, size_t need) {
     if (need <= *have) return RAFT_OK;
     if (*buf) HIP_TRY(hipFree(*buf));
     *buf = nullptr;
@@ -1733,7 +1725,7 @@ static int grow_dev(raft_engine* e, char** buf, size_t* have, size_t need) {
     *have = need;
     return RAFT_OK;
 }
-static int grow_host(raft_engine* e, char** buf, size_t* have, size_t need) {
+int raft_internal_grow_host(raft_engine* e, char** buf, size_t* have, size_t need) {
     if (need <= *have) return RAFT_OK;
     if (*buf) HIP_TRY(hipHostFree(*buf));
     *buf = nullptr;
@@ -1743,52 +1735,40 @@ static int grow_host(raft_engine* e, char** buf, size_t* have, size_t need) {
     *have = need;
     return RAFT_OK;
 }
-int raft_internal_grow_dev(raft_engine* e, char** buf, size_t* have, size_t need) {
-    return grow_dev(e, buf, have, need);
-}
-int raft_internal_grow_host(raft_engine* e, char** buf, size_t* have, size_t need) {
-    return grow_host(e, buf, have, need);
-}
-
-static int check_range(raft_engine* e, int64_t g0, int64_t n) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
-    if (g0 < 0 || n < 0 || g0 + n > e->p.G) return fail(RAFT_ERANGE, "group range outside the engine");
-    return RAFT_OK;
-}
 
 int raft_engine_read_state(raft_engine* e, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
-    if (!out) return fail(RAFT_EINVAL, "null buffer");
+    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
     const size_t bytes = (size_t)n * raft_group_words(e->p.R) * 4;
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, bytes)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, bytes)) return rc;
     int32_t* buf = (int32_t*)e->aux;
     dispatch_R<PackL>(e->p.R, e, g0, n, buf);
     hipError_t err = hipMemcpyAsync(out, buf, bytes, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     return RAFT_OK;
 }
 
 int raft_engine_write_state(raft_engine* e, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
-    if (!in) return fail(RAFT_EINVAL, "null buffer");
+    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     const int W = raft_group_words(e->p.R);
     for (int64_t j = 0; j < n; ++j)              // invariant 0 <= lastIndex <= physLen <= log_cap
         for (int r = 0; r < e->p.R; ++r) {
             const int32_t* f = in + j * W + r * RAFT_NUM_FIELDS;
             if (f[RAFT_F_LAST] < 0 || f[RAFT_F_LAST] > f[RAFT_F_PHYS] || f[RAFT_F_PHYS] > e->p.log_cap)
-                return fail(RAFT_EINVAL, "state violates 0 <= lastIndex <= physLen <= log_cap");
+                return raft_internal_fail(RAFT_EINVAL, "state violates 0 <= lastIndex <= physLen <= log_cap");
         }
     for (int64_t j = 0; j < n; ++j)              // an isolation word: only kernels with NET_ISO from now on
         if (in[j * W + W - 2] != 0) e->iso_written = true;
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
     const size_t bytes = (size_t)n * W * 4;
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, bytes)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, bytes)) return rc;
     int32_t* buf = (int32_t*)e->aux;
     hipError_t err = hipMemcpyAsync(buf, in, bytes, hipMemcpyHostToDevice, e->stream);
     e->cache_valid = false;
@@ -1796,7 +1776,7 @@ int raft_engine_write_state(raft_engine* e, int64_t g0, int64_t n, const int32_t
         dispatch_R<UnpackL>(e->p.R, e, g0, n, buf);
         err = hipStreamSynchronize(e->stream);
     }
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     return RAFT_OK;
 }
 
@@ -1804,7 +1784,7 @@ int raft_engine_write_state(raft_engine* e, int64_t g0, int64_t n, const int32_t
 static int log_image(raft_engine* e, int64_t g0, int64_t n, std::vector<uint2>& tmp, bool to_ring) {
     e->fork_needed = true;
     const size_t cnt = (size_t)n * e->p.R * e->p.log_cap;
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, cnt * 8)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, cnt * 8)) return rc;
     uint2* buf = (uint2*)e->aux;
     hipError_t err = hipSuccess;
     if (to_ring) err = hipMemcpyAsync(buf, tmp.data(), cnt * 8, hipMemcpyHostToDevice, e->stream);
@@ -1815,14 +1795,14 @@ static int log_image(raft_engine* e, int64_t g0, int64_t n, std::vector<uint2>& 
     }
     if (err == hipSuccess && !to_ring) err = hipMemcpyAsync(tmp.data(), buf, cnt * 8, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     return RAFT_OK;
 }
 
 int raft_engine_read_log(raft_engine* e, int64_t g0, int64_t n, int32_t* terms, uint32_t* cmds) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
-    if (!terms || !cmds) return fail(RAFT_EINVAL, "null buffer");
+    if (!terms || !cmds) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));
     const size_t cnt = (size_t)n * e->p.R * e->p.log_cap;
     std::vector<uint2> tmp(cnt);
@@ -1832,9 +1812,9 @@ int raft_engine_read_log(raft_engine* e, int64_t g0, int64_t n, int32_t* terms, 
 }
 
 int raft_engine_write_log(raft_engine* e, int64_t g0, int64_t n, const int32_t* terms, const uint32_t* cmds) {
-    if (int rc = check_range(e, g0, n)) return rc;
+    if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
-    if (!terms || !cmds) return fail(RAFT_EINVAL, "null buffer");
+    if (!terms || !cmds) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));
     const size_t cnt = (size_t)n * e->p.R * e->p.log_cap;
     std::vector<uint2> tmp(cnt);
@@ -1844,18 +1824,18 @@ int raft_engine_write_log(raft_engine* e, int64_t g0, int64_t n, const int32_t* 
 }
 
 int raft_engine_digest(raft_engine* e, uint64_t* out) {
-    if (!e) return fail(RAFT_EINVAL, "null engine");
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     return raft_engine_digest_range(e, 0, e->p.G, out);
 }
 
 int raft_engine_digest_range(raft_engine* e, int64_t g0, int64_t n, uint64_t* out) {
-    if (int rc = check_range(e, g0, n)) return rc;
-    if (!out) return fail(RAFT_EINVAL, "null argument");
+    if (int rc = check_groups(e, g0, n)) return rc;
+    if (!out) return raft_internal_fail(RAFT_EINVAL, "null argument");
     *out = 0;
     if (n == 0) return RAFT_OK;
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, 8)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, 8)) return rc;
     unsigned long long* d = (unsigned long long*)e->aux;
     hipError_t err = hipMemsetAsync(d, 0, 8, e->stream);
     if (err == hipSuccess) {
@@ -1863,21 +1843,23 @@ int raft_engine_digest_range(raft_engine* e, int64_t g0, int64_t n, uint64_t* ou
         err = hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, e->stream);
     }
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     return RAFT_OK;
 }
 
 int raft_engine_traffic_probe(raft_engine* e, int32_t kind, int64_t* bytes_read, int64_t* bytes_written) {
-    if (!e || !bytes_read || !bytes_written) return fail(RAFT_EINVAL, "null argument");
+    if (!e || !bytes_read || !bytes_written) return raft_internal_fail(RAFT_EINVAL, "null argument");
     if (kind < 0 || kind > 3)
-        return fail(RAFT_EINVAL, "kind must be 0 (state), 1 (log stores), 2 (scattered loads) or 3 (scattered stores)");
-    if (kind == 1 && e->p.log_window) return fail(RAFT_EINVAL, "the log-store probe needs a flat log (log_window 0)");
+        return raft_internal_fail(RAFT_EINVAL,
+                                  "kind must be 0 (state), 1 (log stores), 2 (scattered loads) or 3 (scattered stores)");
+    if (kind == 1 && e->p.log_window)
+        return raft_internal_fail(RAFT_EINVAL, "the log-store probe needs a flat log (log_window 0)");
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
     if (kind >= 2) {
         // engine-owned scratch (the accessors' staging, grow-only): the state is untouched
         const size_t sz = (size_t)32 << SCATTER_LOG2;
-        if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, sz)) return rc;
+        if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, sz)) return rc;
         scatter_probe_kernel<<<SCATTER_N / BLOCK, BLOCK, 0, e->stream>>>((uint32_t*)e->aux, (int)kind);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1885,7 +1867,7 @@ int raft_engine_traffic_probe(raft_engine* e, int32_t kind, int64_t* bytes_read,
         *bytes_written = kind == 3 ? (int64_t)SCATTER_N * 32 : 0;
         return RAFT_OK;
     }
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, 8)) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, 8)) return rc;
     unsigned long long* d = (unsigned long long*)e->aux;
     unsigned long long h = 0;
     hipError_t err = hipMemsetAsync(d, 0, 8, e->stream);
@@ -1895,7 +1877,7 @@ int raft_engine_traffic_probe(raft_engine* e, int32_t kind, int64_t* bytes_read,
     }
     if (err == hipSuccess) err = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     const int64_t state = e->p.G * ((int64_t)e->p.R * 16 * ST_QUADS + 4 * GX_WORDS);
     *bytes_read = kind == 0 ? state : 4 * e->p.G * e->p.R;               // kind 1 reads physLen
     *bytes_written = kind == 0 ? state : 8 * (int64_t)h;
@@ -1903,13 +1885,13 @@ int raft_engine_traffic_probe(raft_engine* e, int32_t kind, int64_t* bytes_read,
 }
 
 int raft_engine_check_log_matching(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, int64_t* mismatched) {
-    if (int rc = check_range(e, g0, n)) return rc;
-    if (!mismatched) return fail(RAFT_EINVAL, "null argument");
+    if (int rc = check_groups(e, g0, n)) return rc;
+    if (!mismatched) return raft_internal_fail(RAFT_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
     *mismatched = 0;
     if (n == 0) return RAFT_OK;
-    if (int rc = grow_dev(e, &e->aux, &e->aux_bytes, 8 + (flags ? (size_t)n : 0))) return rc;
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, 8 + (flags ? (size_t)n : 0))) return rc;
     void* d = e->aux;
     unsigned long long* cnt = (unsigned long long*)d;
     uint8_t* fl = flags ? (uint8_t*)d + 8 : nullptr;
@@ -1922,7 +1904,7 @@ int raft_engine_check_log_matching(raft_engine* e, int64_t g0, int64_t n, uint8_
     if (err == hipSuccess) err = hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess && flags) err = hipMemcpyAsync(flags, fl, (size_t)n, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) return fail(RAFT_EDEVICE, hipGetErrorString(err));
+    if (err != hipSuccess) return raft_internal_fail(RAFT_EDEVICE, hipGetErrorString(err));
     *mismatched = (int64_t)h;
     return RAFT_OK;
 }

@@ -1,13 +1,22 @@
-// raft_engine_impl.h — internal to the engine library: what raft_engine.hip
-// (the step kernel, the accessors, the C-ABI), raft_batch.hip (the handler
-// batches, include/raft_engine.h raft_*_batch*), raft_apply.hip (the
-// committed-entry drain), raft_client.hip (the leader directory, routed
-// proposals and tickets), raft_sm.hip (the replicated state machine),
-// raft_fault.hip (replica restart) and raft_read.hip (linearizable reads) share -- the engine object, the HBM indexing helpers, a replica's quad load /
-// store, the leader lookup and the error / staging entry points.  Not installed.
+// raft_engine_impl.h — internal to the engine library, not installed: what its
+// translation units share.
+//   raft_engine.hip   the step kernel, the accessors, the C-ABI
+//   raft_batch.hip    the handler batches (include/raft_engine.h raft_*_batch*)
+//   raft_apply.hip    the committed-entry drain
+//   raft_client.hip   the leader directory, routed proposals and tickets
+//   raft_sm.hip       the replicated state machine
+//   raft_fault.hip    replica restart
+//   raft_read.hip     linearizable reads
+// Device side: the HBM indexing helpers, a replica's quad load / store, the
+// leader lookups, the committed prefix.  Host side: the engine object and the
+// call plumbing of the entry points -- HIP_TRY, the argument checks, the
+// staging of a host call's arrays (Staged), the readback of a call's status
+// words or totals (DevWords).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort_config.hpp>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -24,12 +33,27 @@ extern "C" int raft_internal_grow_host(raft_engine* e, char** buf, size_t* have,
 // if a host write left it stale (cache_valid false)
 void raft_internal_ensure_cache(raft_engine* e);
 
+#define HIP_TRY(expr)                                                                                    \
+    do {                                                                                                 \
+        hipError_t _e = (expr);                                                                          \
+        if (_e != hipSuccess)                                                                            \
+            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// rocprim's radix sort takes its merge-sort path up to 2^20 items (one
+// block sort and ~10 merge passes over the whole array, 21 dispatches at 10^6
+// messages); a merge limit of 0 keeps it on the onesweep path (a histogram
+// pass and one pass per 8 key bits).
+using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
+                                              rocprim::default_config, 0>;
+
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr int WAVES_PER_BLOCK = BLOCK / 64;
 
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // field f of replica idx = g * R + r in the state quads (DevParams::st,
 // raft_step.h FIELD_SLOT): word f & 3 of quad f >> 2 of the replica's slots
@@ -50,6 +74,11 @@ __device__ __forceinline__ LogView log_of(const DevParams& p, int64_t idx) {
     const int64_t w = g / gpw;
     const int lane = (int)(g - w * gpw) * p.R + (int)(idx - g * p.R);
     return LogView{p.log + (w * 64 + lane) * (int64_t)p.nslots, (uint32_t)p.nslots, p.wmask, p.cap, p.W};
+}
+
+// the committed prefix of a replica, in entries: min(commitIndex, lastIndex) within 0..log_cap
+__device__ __forceinline__ int32_t committed_hi(const DevParams& p, int32_t commit, int32_t last) {
+    return max(0, min(min(commit, last), p.cap));
 }
 
 // ---- one replica in registers: the handler batches (raft_batch.hip) and the
@@ -98,19 +127,25 @@ __device__ __forceinline__ void store_rep(const RepState& x, const RepQuads& o, 
     if (!VOTE_ONLY && differ(q2, o.q2)) *quad(p, 2, idx) = q2;
 }
 
+// The R role words of group g: reads of quad 0 (which also holds currentTerm),
+// all R in flight at once: unconditional loads at a clamped index, as
+// bucket_tile_kernel's.  q[r] is replica r's for r < R.
+__device__ __forceinline__ void load_roles(const DevParams& p, int64_t g, int4 (&q)[RAFT_MAX_R]) {
+    const int R = p.R;
+    const int4* q0 = quad(p, 0, g * R);
+#pragma unroll
+    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = q0[min(r, R - 1)];
+}
+
 // The group's leader as RAFT_CMD_LOWEST_LEADER chooses it: the lowest replica
-// index whose role is LEADER.  The R role words are reads of quad 0 (which
-// also holds currentTerm), all R in flight at once: unconditional loads at a
-// clamped index, as bucket_tile_kernel's.
+// index whose role is LEADER.
 struct Lead {
     int32_t r, n, term;
 };
 __device__ __forceinline__ Lead find_leader(const DevParams& p, int64_t g) {
-    const int R = p.R;
-    const int64_t base = g * R;
     int4 q[RAFT_MAX_R];
-#pragma unroll
-    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
+    load_roles(p, g, q);
+    const int R = p.R;
     Lead l{-1, 0, 0};
 #pragma unroll
     for (int r = RAFT_MAX_R - 1; r >= 0; --r) {                       // descending: the lowest id is taken last
@@ -127,13 +162,11 @@ __device__ __forceinline__ Lead find_leader(const DevParams& p, int64_t g) {
 // of the replicas whose role is LEADER the one with the highest currentTerm,
 // the lowest index among equals.  Not find_leader's rule: a deposed leader
 // keeps its role until it hears of the new term, and at a lower index it would
-// shadow its successor.  The same R loads of quad 0, all in flight at once.
+// shadow its successor.
 __device__ __forceinline__ Lead find_newest_leader(const DevParams& p, int64_t g) {
-    const int R = p.R;
-    const int64_t base = g * R;
     int4 q[RAFT_MAX_R];
-#pragma unroll
-    for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
+    load_roles(p, g, q);
+    const int R = p.R;
     Lead l{-1, 0, 0};
 #pragma unroll
     for (int r = RAFT_MAX_R - 1; r >= 0; --r) {                       // descending: of equal terms the lowest id is taken last
@@ -280,15 +313,111 @@ struct raft_engine {
 };
 
 namespace {
-// groups [g0, g0 + n) of a non-null engine (the accessors of raft_apply.hip and raft_sm.hip)
+// ---- argument checks of the entry points: each sets raft_last_error()
+// groups [g0, g0 + n) of an engine
 inline int check_groups(raft_engine* e, int64_t g0, int64_t n) {
     if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
     if (g0 < 0 || n < 0 || g0 + n > e->p.G) return raft_internal_fail(RAFT_ERANGE, "group range outside the engine");
     return RAFT_OK;
 }
-// the machine's allocation (raft_engine::sm, raft_sm.hip): a header of SM_HDR_BYTES, the heads [G * R] (int4:
-// applied, lost, hash lo, hash hi), the registers [G * R][sm_slots]; raft_fault.hip zeroes a restarted replica's
-constexpr size_t SM_HDR_BYTES = 4096;
-inline int4* sm_heads_of(raft_engine* e) { return (int4*)(e->sm + SM_HDR_BYTES); }
-inline uint32_t* sm_regs_of(raft_engine* e) { return (uint32_t*)(e->sm + SM_HDR_BYTES + al256((size_t)e->dp.GR * 16)); }
+// a batch of n messages; any_null: one of its buffers is null (an error only when n > 0)
+inline int check_args(raft_engine* e, int64_t n, bool any_null) {
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (n < 0) return raft_internal_fail(RAFT_EINVAL, "negative batch");
+    if (n > 0x7FFFFFFF) return raft_internal_fail(RAFT_EINVAL, "batch larger than 2^31 - 1 messages");
+    if (n > 0 && any_null) return raft_internal_fail(RAFT_EINVAL, "null buffer");
+    return RAFT_OK;
+}
+// an engine whose state machine is configured
+inline int check_sm(raft_engine* e) {
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (!e->sm)
+        return raft_internal_fail(RAFT_EINVAL, "the state machine is not configured (raft_engine_sm_configure first)");
+    return RAFT_OK;
+}
+
+// ---- a host call's arrays: copied into the engine's page-locked staging
+// (hst), moved with one DMA to their device copies (cio); the records come
+// back the same way.  Layout of both: up to 3 inputs, 256-byte aligned each,
+// then the output.
+struct Staged {
+    size_t off[3];
+    size_t out_off, out_bytes;
+};
+inline int stage_in(raft_engine* e, const void* const* src, const size_t* bytes, int k, size_t out_bytes, Staged& s) {
+    size_t at = 0;
+    for (int i = 0; i < k; ++i) {
+        s.off[i] = at;
+        at += al256(bytes[i]);
+    }
+    s.out_off = at;
+    s.out_bytes = out_bytes;
+    if (int rc = raft_internal_grow_dev(e, &e->cio, &e->cio_bytes, at + al256(out_bytes))) return rc;
+    if (int rc = raft_internal_grow_host(e, &e->hst, &e->hst_bytes, at + al256(out_bytes))) return rc;
+    for (int i = 0; i < k; ++i) std::memcpy(e->hst + s.off[i], src[i], bytes[i]);
+    HIP_TRY(hipMemcpyAsync(e->cio, e->hst, at, hipMemcpyHostToDevice, e->stream));
+    return RAFT_OK;
+}
+// the output's way back in its two halves -- the DMA into hst, and after a
+// stream synchronize the copy to the caller -- for a call that decides in
+// between whether the caller's memory is written (raft_engine_sm_get)
+inline int stage_out_dma(raft_engine* e, const Staged& s) {
+    HIP_TRY(hipMemcpyAsync(e->hst + s.out_off, e->cio + s.out_off, s.out_bytes, hipMemcpyDeviceToHost, e->stream));
+    return RAFT_OK;
+}
+inline void stage_out_copy(raft_engine* e, const Staged& s, void* dst) { std::memcpy(dst, e->hst + s.out_off, s.out_bytes); }
+inline int stage_out(raft_engine* e, const Staged& s, void* dst) {
+    if (int rc = stage_out_dma(e, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    stage_out_copy(e, s, dst);
+    return RAFT_OK;
+}
+
+// ---- the status words or totals a call's kernels leave on the device:
+// STRIPES lines of LINE words of T, words 0 .. WORDS - 1 of a line in use.
+// zero() clears them on the engine stream before the kernels; fetch() copies
+// them back, waits for the stream and folds the stripes word by word into w[]
+// (a sum, or an OR).  Why stripes: when most waves of a large call have
+// something to report, one atomic each on a single word serialises them
+// ("Measured", has the figure); a wave uses stripe (its index
+// mod STRIPES) instead.  One stripe is the plain case: it lands in the engine's
+// page-locked words (below the step kernel's, word 8), the striped ones in a
+// local array.
+template <typename T, int STRIPES, int LINE, int WORDS, bool SUM>
+struct DevWords {
+    static constexpr size_t BYTES = (size_t)STRIPES * LINE * sizeof(T);
+    static_assert(WORDS <= LINE && (STRIPES > 1 || BYTES <= 8 * sizeof(unsigned int)), "one stripe fits bflags_host");
+    T* dev;
+    T w[WORDS];
+    int zero(raft_engine* e, void* at) {
+        dev = (T*)at;
+        HIP_TRY(hipMemsetAsync(dev, 0, BYTES, e->stream));
+        return RAFT_OK;
+    }
+    int fetch(raft_engine* e) {
+        T local[STRIPES > 1 ? STRIPES * LINE : 1];
+        T* h = STRIPES > 1 ? local : (T*)e->bflags_host;
+        HIP_TRY(hipMemcpyAsync(h, dev, BYTES, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (int i = 0; i < WORDS; ++i) {
+            w[i] = 0;
+            for (int k = 0; k < STRIPES; ++k) w[i] = SUM ? w[i] + h[k * LINE + i] : w[i] | h[k * LINE + i];
+        }
+        return RAFT_OK;
+    }
+};
+// the totals of a state-machine apply (the header of raft_engine::sm) and of a restart: 64 lines of 64 bytes,
+// 64-bit sums.  Their kernels index it with these.
+constexpr int HDR_LINE = 8, HDR_STRIPES = 64;
+using Totals = DevWords<unsigned long long, HDR_STRIPES, HDR_LINE, 3, true>;
+
+// the machine's allocation (raft_engine::sm, raft_sm.hip): the totals header, the heads [G * R] (int4: applied,
+// lost, hash lo, hash hi), the registers [G * R][sm_slots]; raft_fault.hip zeroes a restarted replica's
+inline int4* sm_heads_of(raft_engine* e) { return (int4*)(e->sm + Totals::BYTES); }
+inline uint32_t* sm_regs_of(raft_engine* e) { return (uint32_t*)(e->sm + Totals::BYTES + al256((size_t)e->dp.GR * 16)); }
+inline int log2_slots(const raft_engine* e) {
+    int l = 0;
+    while ((1 << l) < e->sm_slots) ++l;
+    return l;
+}
 }  // namespace

@@ -41,18 +41,10 @@ using namespace raft;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 static_assert(sizeof(raft_restart_info) == 32, "record layout of the C-ABI");
 
-// the header: HDR_STRIPES lines of 64 bytes, words 0..2 of a line
-constexpr int HDR_RESTARTED = 0, HDR_LEADERS = 1, HDR_DROPPED = 2, HDR_LINE = 8, HDR_STRIPES = 64;
-constexpr size_t HDR_BYTES = (size_t)HDR_STRIPES * HDR_LINE * 8;
+// the totals of a restart (Totals, raft_engine_impl.h): these words of a wave's stripe
+constexpr int HDR_RESTARTED = 0, HDR_LEADERS = 1, HDR_DROPPED = 2;
 constexpr int32_t MAX_DOWN_STEPS = (1 << 23) - 1;
 
 struct RestartArgs {
@@ -188,13 +180,13 @@ int restart(raft_engine* e, int64_t g0, int64_t n, int how, const uint8_t* mask,
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;                           // later step launches wait for the restart
     // staging: the header, then the device copy of a host mask
-    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, HDR_BYTES + (how == SEL_HOST ? (size_t)n : 0)))
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Totals::BYTES + (how == SEL_HOST ? (size_t)n : 0)))
         return rc;
-    unsigned long long* hdr = (unsigned long long*)e->aux;
-    HIP_TRY(hipMemsetAsync(hdr, 0, HDR_BYTES, e->stream));
+    Totals tot;
+    if (int rc = tot.zero(e, e->aux)) return rc;
     if (how == SEL_HOST) {
-        HIP_TRY(hipMemcpyAsync(e->aux + HDR_BYTES, mask, (size_t)n, hipMemcpyHostToDevice, e->stream));
-        mask = (const uint8_t*)(e->aux + HDR_BYTES);
+        HIP_TRY(hipMemcpyAsync(e->aux + Totals::BYTES, mask, (size_t)n, hipMemcpyHostToDevice, e->stream));
+        mask = (const uint8_t*)(e->aux + Totals::BYTES);
     }
     RestartArgs a{};
     a.g0 = g0;
@@ -208,19 +200,15 @@ int restart(raft_engine* e, int64_t g0, int64_t n, int how, const uint8_t* mask,
     if (e->sm) {
         a.heads = sm_heads_of(e);
         a.regs = sm_regs_of(e);
-        while ((1 << a.logS) < e->sm_slots) ++a.logS;
+        a.logS = log2_slots(e);
     }
-    a.hdr = hdr;
+    a.hdr = tot.dev;
     by_R<RestartL>(e->p.R, e, a);
     HIP_TRY(hipGetLastError());
-    unsigned long long h[HDR_STRIPES * HDR_LINE];
-    HIP_TRY(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int k = 0; k < HDR_STRIPES; ++k) {
-        info->restarted += (int64_t)h[k * HDR_LINE + HDR_RESTARTED];
-        info->leaders += (int64_t)h[k * HDR_LINE + HDR_LEADERS];
-        info->entries_dropped += (int64_t)h[k * HDR_LINE + HDR_DROPPED];
-    }
+    if (int rc = tot.fetch(e)) return rc;
+    info->restarted = (int64_t)tot.w[HDR_RESTARTED];
+    info->leaders = (int64_t)tot.w[HDR_LEADERS];
+    info->entries_dropped = (int64_t)tot.w[HDR_DROPPED];
     if (down_steps > 0 && info->restarted > 0) e->iso_written = true;   // an isolation word: NET_ISO kernels from now on
     return RAFT_OK;
 }

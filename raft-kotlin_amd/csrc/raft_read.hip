@@ -21,7 +21,6 @@
 // ballot, into the wave's stripe of 64.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "raft_engine_impl.h"
@@ -30,22 +29,14 @@ using namespace raft;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 static_assert(sizeof(raft_read_ticket) == 16 && sizeof(raft_read_result) == 16, "record layouts of the C-ABI");
 
 // The status words of a call, as RW_STRIPES stripes of one 64-byte line each
 // (words 0..2 of a line): a wave ORs into stripe (its index mod RW_STRIPES) and
-// the host ORs the stripes (raft_sm.hip's header, for the same reason).  When
-// most waves of a large batch have something to report, one atomic each on a
-// single word serialises them ("Measured", has the figure).
+// the host ORs the stripes (DevWords, raft_engine_impl.h, says why), at the
+// head of cli.
 enum { RW_RANGE = 0, RW_INVAL = 1, RW_WINDOW = 2, RW_WORDS = 3, RW_LINE = 16, RW_STRIPES = 64 };
-constexpr size_t RW_BYTES = (size_t)RW_STRIPES * RW_LINE * 4;
+using Status = DevWords<unsigned int, RW_STRIPES, RW_LINE, RW_WORDS, false>;
 
 // OR 1 into status word `w` of the wave's stripe, once per wave: every lane of
 // the wave calls this.  The range word stays in stripe 0, where the begin pass
@@ -79,7 +70,7 @@ __global__ __launch_bounds__(BLOCK) void read_begin_kernel(DevParams p, const in
             const int64_t idx = g * p.R + l.r;
             const int4 q1 = *quad(p, 1, idx);                           // lastIndex, physLen
             const int32_t commit = quad(p, 2, idx)->x;
-            const int32_t hi = max(0, min(min(commit, q1.x), p.cap));   // the committed prefix (the drain's)
+            const int32_t hi = committed_hi(p, commit, q1.x);
             int32_t st;
             if (hi == 0) {
                 st = RAFT_READ_TERM_UNCOMMITTED;
@@ -120,10 +111,9 @@ __global__ __launch_bounds__(BLOCK) void read_serve_kernel(DevParams p, int S, c
             rec.y = RAFT_READ_NONE;
         } else {
             const int R = p.R;
-            const int64_t base = g * R, idx = base + tk.x;
             int4 q[RAFT_MAX_R];
-#pragma unroll
-            for (int r = 0; r < RAFT_MAX_R; ++r) q[r] = *quad(p, 0, base + min(r, R - 1));
+            load_roles(p, g, q);
+            const int64_t idx = g * R + tk.x;
             const int4 hd = heads[idx];                                 // applied, lost, hash
             const uint32_t v = regs[idx * S + (k & (uint32_t)(S - 1))];
             int32_t agree = 0;
@@ -157,54 +147,23 @@ __global__ __launch_bounds__(BLOCK) void read_serve_kernel(DevParams p, int S, c
     wave_flag(flags, RW_INVAL, live && g_ok && !t_ok);
 }
 
-int check_args(raft_engine* e, int64_t n, bool any_null) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (n < 0) return raft_internal_fail(RAFT_EINVAL, "negative batch");
-    if (n > 0x7FFFFFFF) return raft_internal_fail(RAFT_EINVAL, "batch larger than 2^31 - 1 messages");
-    if (n > 0 && any_null) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    return RAFT_OK;
-}
-
-int check_sm(raft_engine* e) {
-    if (e && !e->sm)
-        return raft_internal_fail(RAFT_EINVAL, "the state machine is not configured (raft_engine_sm_configure first)");
-    return RAFT_OK;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-// the status words of a finished call: the stripes OR-ed into words [RW_WORDS]
-int fetch_flags(raft_engine* e, const unsigned int* flags, unsigned int* words) {
-    unsigned int h[RW_STRIPES * RW_LINE];
-    HIP_TRY(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int w = 0; w < RW_WORDS; ++w) {
-        words[w] = 0;
-        for (int k = 0; k < RW_STRIPES; ++k) words[w] |= h[k * RW_LINE + w];
-    }
-    return RAFT_OK;
-}
-
-int zeroed_flags(raft_engine* e, unsigned int** flags) {
-    if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, RW_BYTES)) return rc;
-    *flags = (unsigned int*)e->cli;
-    HIP_TRY(hipMemsetAsync(*flags, 0, RW_BYTES, e->stream));
-    return RAFT_OK;
+int zeroed_status(raft_engine* e, Status& st) {
+    if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, Status::BYTES)) return rc;
+    return st.zero(e, e->cli);
 }
 
 int begin_dev(raft_engine* e, const int64_t* group, raft_read_ticket* ticket, int n) {
     e->fork_needed = true;                          // later step launches wait for these reads of the state and logs
-    unsigned int* flags;
-    if (int rc = zeroed_flags(e, &flags)) return rc;
+    Status st;
+    if (int rc = zeroed_status(e, st)) return rc;
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    read_range_kernel<<<grid, BLOCK, 0, e->stream>>>(group, n, e->p.G, flags);
-    read_begin_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, group, (int4*)ticket, n, flags);
+    read_range_kernel<<<grid, BLOCK, 0, e->stream>>>(group, n, e->p.G, st.dev);
+    read_begin_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, group, (int4*)ticket, n, st.dev);
     HIP_TRY(hipGetLastError());
-    unsigned int words[RW_WORDS];
-    if (int rc = fetch_flags(e, flags, words)) return rc;
-    if (words[RW_RANGE])
+    if (int rc = st.fetch(e)) return rc;
+    if (st.w[RW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a read's group is outside the engine; no ticket was written");
-    if (words[RW_WINDOW])
+    if (st.w[RW_WINDOW])
         return raft_internal_fail(RAFT_EWINDOW, "a leader's last committed slot is below its log_window (its ticket is UNKNOWN)");
     return RAFT_OK;
 }
@@ -212,46 +171,16 @@ int begin_dev(raft_engine* e, const int64_t* group, raft_read_ticket* ticket, in
 int serve_dev(raft_engine* e, const int64_t* group, const raft_read_ticket* ticket, const uint32_t* key,
               raft_read_result* out, int n) {
     e->fork_needed = true;
-    unsigned int* flags;
-    if (int rc = zeroed_flags(e, &flags)) return rc;
+    Status st;
+    if (int rc = zeroed_status(e, st)) return rc;
     read_serve_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
-        e->dp, e->sm_slots, sm_heads_of(e), sm_regs_of(e), group, (const int4*)ticket, key, (int4*)out, n, flags);
+        e->dp, e->sm_slots, sm_heads_of(e), sm_regs_of(e), group, (const int4*)ticket, key, (int4*)out, n, st.dev);
     HIP_TRY(hipGetLastError());
-    unsigned int words[RW_WORDS];
-    if (int rc = fetch_flags(e, flags, words)) return rc;
-    if (words[RW_RANGE])
+    if (int rc = st.fetch(e)) return rc;
+    if (st.w[RW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a read's group is outside the engine (its record is INVALID)");
-    if (words[RW_INVAL])
+    if (st.w[RW_INVAL])
         return raft_internal_fail(RAFT_EINVAL, "a ticket's replica or read_index is outside the engine (its record is INVALID)");
-    return RAFT_OK;
-}
-
-// A host call's arrays, as the client path stages them: copied into the
-// engine's page-locked staging (hst), moved with one DMA to their device
-// copies (cio); the records come back the same way.  Layout of both: the
-// inputs, 256-byte aligned each, then the output.
-struct Staged {
-    size_t off[3];
-    size_t out_off, out_bytes;
-};
-int stage_in(raft_engine* e, const void* const* src, const size_t* bytes, int k, size_t out_bytes, Staged& s) {
-    size_t at = 0;
-    for (int i = 0; i < k; ++i) {
-        s.off[i] = at;
-        at += al256(bytes[i]);
-    }
-    s.out_off = at;
-    s.out_bytes = out_bytes;
-    if (int rc = raft_internal_grow_dev(e, &e->cio, &e->cio_bytes, at + al256(out_bytes))) return rc;
-    if (int rc = raft_internal_grow_host(e, &e->hst, &e->hst_bytes, at + al256(out_bytes))) return rc;
-    for (int i = 0; i < k; ++i) std::memcpy(e->hst + s.off[i], src[i], bytes[i]);
-    HIP_TRY(hipMemcpyAsync(e->cio, e->hst, at, hipMemcpyHostToDevice, e->stream));
-    return RAFT_OK;
-}
-int stage_out(raft_engine* e, const Staged& s, void* dst) {
-    HIP_TRY(hipMemcpyAsync(e->hst + s.out_off, e->cio + s.out_off, s.out_bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    std::memcpy(dst, e->hst + s.out_off, s.out_bytes);
     return RAFT_OK;
 }
 

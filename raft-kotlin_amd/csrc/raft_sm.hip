@@ -30,7 +30,6 @@
 //   check   one thread per group: its R heads
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "raft_engine_impl.h"
@@ -39,28 +38,14 @@ using namespace raft;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return raft_internal_fail(RAFT_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 static_assert(sizeof(raft_sm_info) == 32 && sizeof(raft_sm_head) == 16 && sizeof(raft_sm_value) == 16,
               "record layouts of the C-ABI");
 
-// The header: the totals of an apply, as HDR_STRIPES stripes of one 64-byte line each (words 0..2 of a
-// line).  A wave adds to stripe (its index mod HDR_STRIPES) and the host sums them: every wave with
-// entries adds to `applied`, and on one word the atomics of every wave of a large engine serialise
-constexpr int HDR_APPLIED = 0, HDR_LOST = 1, HDR_REGRESSED = 2, HDR_LINE = 8, HDR_STRIPES = 64;
-constexpr size_t HDR_BYTES = (size_t)HDR_STRIPES * HDR_LINE * 8;
-static_assert(HDR_BYTES == SM_HDR_BYTES, "the header's size is shared with raft_fault.hip (raft_engine_impl.h)");
+// The header: the totals of an apply (Totals, raft_engine_impl.h), these words of a wave's stripe.  Every
+// wave with entries adds to `applied`
+constexpr int HDR_APPLIED = 0, HDR_LOST = 1, HDR_REGRESSED = 2;
 constexpr uint64_t SM_P = 0xD1342543DE82EF95ull, SM_GOLD = 0x9E3779B97F4A7C15ull;
 constexpr int PW_WORDS = 66;                                          // P^0 .. P^64 and a pad word, per wave
-
-// the machine's allocation: header, heads (int4: applied, lost, hash lo, hash hi), registers
-int4* heads_of(raft_engine* e) { return sm_heads_of(e); }
-uint32_t* regs_of(raft_engine* e) { return sm_regs_of(e); }
 
 __device__ __forceinline__ uint64_t sm_x(int32_t i, uint32_t t, uint32_t c) {
     uint64_t z = ((uint64_t)t << 32 | c) + (uint64_t)(uint32_t)i * SM_GOLD;
@@ -107,7 +92,7 @@ __global__ __launch_bounds__(BLOCK) void sm_apply_kernel(DevParams p, Sel s, int
     if (mine) {
         const int32_t commit = p.st[fidx(p, RAFT_F_COMMIT, my_idx)];
         const int32_t last = p.st[fidx(p, RAFT_F_LAST, my_idx)];
-        const int32_t hi = max(0, min(min(commit, last), p.cap));      // the committed prefix (the drain's)
+        const int32_t hi = committed_hi(p, commit, last);
         if (p.W != FLAT_W) {                                           // a ring: entries below the window are gone
             const int32_t wl = max(0, p.st[fidx(p, RAFT_F_PHYS, my_idx)] - p.W);
             if (wl > lo && hi > lo) {
@@ -227,8 +212,10 @@ __global__ __launch_bounds__(BLOCK) void sm_apply_kernel(DevParams p, Sel s, int
                                   (int32_t)(uint32_t)(hash >> 32));
 }
 
+// the status word of a get (DevWords, raft_engine_impl.h: one stripe), at the head of cli
 enum { GW_RANGE = 0, GW_WORDS = 1 };
 constexpr size_t GW_BYTES = 256;
+using GetStatus = DevWords<unsigned int, 1, GW_WORDS, GW_WORDS, false>;
 
 __global__ __launch_bounds__(BLOCK) void sm_get_kernel(DevParams p, int S, const int4* __restrict__ heads,
                                                        const uint32_t* __restrict__ regs,
@@ -285,16 +272,9 @@ template <int R> struct ApplyL {
         const int64_t tiles = (s.N + 63) / 64;
         const unsigned grid = (unsigned)((tiles + wpb - 1) / wpb);
         const size_t lds = (size_t)wpb * (PW_WORDS + 64 * S) * 8;
-        sm_apply_kernel<R><<<grid, wpb * 64, lds, e->stream>>>(e->dp, s, logS, heads_of(e), regs_of(e), hdr);
+        sm_apply_kernel<R><<<grid, wpb * 64, lds, e->stream>>>(e->dp, s, logS, sm_heads_of(e), sm_regs_of(e), hdr);
     }
 };
-
-int check_sm(raft_engine* e) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (!e->sm)
-        return raft_internal_fail(RAFT_EINVAL, "the state machine is not configured (raft_engine_sm_configure first)");
-    return RAFT_OK;
-}
 
 }  // namespace
 
@@ -314,7 +294,7 @@ int raft_engine_sm_configure(raft_engine* e, int32_t slots) {
     }
     if (slots == 0) return RAFT_OK;
     if (!e->sm) {
-        const size_t bytes = HDR_BYTES + al256((size_t)e->dp.GR * 16) + al256((size_t)e->dp.GR * slots * 4);
+        const size_t bytes = Totals::BYTES + al256((size_t)e->dp.GR * 16) + al256((size_t)e->dp.GR * slots * 4);
         if (hipMalloc((void**)&e->sm, bytes) != hipSuccess) {
             e->sm = nullptr;
             return raft_internal_fail(RAFT_ENOMEM, "hipMalloc of " + std::to_string(bytes) +
@@ -338,22 +318,16 @@ int raft_engine_sm_apply(raft_engine* e, int64_t g0, int64_t n, int32_t replica,
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;                           // later step launches wait for these reads of the state and logs
     const Sel s{g0, replica < 0 ? n * e->p.R : n, replica};
-    int logS = 0;
-    while ((1 << logS) < e->sm_slots) ++logS;
-    unsigned long long* hdr = (unsigned long long*)e->sm;
-    HIP_TRY(hipMemsetAsync(hdr, 0, HDR_BYTES, e->stream));
+    Totals tot;
+    if (int rc = tot.zero(e, e->sm)) return rc;
     if (e->sm_timing) HIP_TRY(hipEventRecord(e->ev_sm[0], e->stream));
-    by_R<ApplyL>(e->p.R, e, s, logS, hdr);
+    by_R<ApplyL>(e->p.R, e, s, log2_slots(e), tot.dev);
     HIP_TRY(hipGetLastError());
     if (e->sm_timing) HIP_TRY(hipEventRecord(e->ev_sm[1], e->stream));
-    unsigned long long h[HDR_STRIPES * HDR_LINE];
-    HIP_TRY(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int k = 0; k < HDR_STRIPES; ++k) {
-        info->applied += (int64_t)h[k * HDR_LINE + HDR_APPLIED];
-        info->lost += (int64_t)h[k * HDR_LINE + HDR_LOST];
-        info->regressed += (int64_t)h[k * HDR_LINE + HDR_REGRESSED];
-    }
+    if (int rc = tot.fetch(e)) return rc;
+    info->applied = (int64_t)tot.w[HDR_APPLIED];
+    info->lost = (int64_t)tot.w[HDR_LOST];
+    info->regressed = (int64_t)tot.w[HDR_REGRESSED];
     if (info->lost > 0)
         return raft_internal_fail(RAFT_EWINDOW, std::to_string(info->lost) +
                                                     " committed entries left the log window unapplied (skipped)");
@@ -367,8 +341,8 @@ int raft_engine_sm_read(raft_engine* e, int64_t g0, int64_t n, raft_sm_head* hea
     HIP_TRY(hipSetDevice(e->device));
     // replicas are indexed g * R + r: the range is one contiguous run of heads and of registers
     const size_t r0 = (size_t)g0 * e->p.R, rn = (size_t)n * e->p.R, S = (size_t)e->sm_slots;
-    if (heads) HIP_TRY(hipMemcpyAsync(heads, heads_of(e) + r0, rn * 16, hipMemcpyDeviceToHost, e->stream));
-    if (regs) HIP_TRY(hipMemcpyAsync(regs, regs_of(e) + r0 * S, rn * S * 4, hipMemcpyDeviceToHost, e->stream));
+    if (heads) HIP_TRY(hipMemcpyAsync(heads, sm_heads_of(e) + r0, rn * 16, hipMemcpyDeviceToHost, e->stream));
+    if (regs) HIP_TRY(hipMemcpyAsync(regs, sm_regs_of(e) + r0 * S, rn * S * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return RAFT_OK;
 }
@@ -385,8 +359,8 @@ int raft_engine_sm_write(raft_engine* e, int64_t g0, int64_t n, const raft_sm_he
             if (heads[k].lost < 0) return raft_internal_fail(RAFT_EINVAL, "lost must be >= 0");
         }
     HIP_TRY(hipSetDevice(e->device));
-    if (heads) HIP_TRY(hipMemcpyAsync(heads_of(e) + r0, heads, rn * 16, hipMemcpyHostToDevice, e->stream));
-    if (regs) HIP_TRY(hipMemcpyAsync(regs_of(e) + r0 * S, regs, rn * S * 4, hipMemcpyHostToDevice, e->stream));
+    if (heads) HIP_TRY(hipMemcpyAsync(sm_heads_of(e) + r0, heads, rn * 16, hipMemcpyHostToDevice, e->stream));
+    if (regs) HIP_TRY(hipMemcpyAsync(sm_regs_of(e) + r0 * S, regs, rn * S * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return RAFT_OK;
 }
@@ -394,35 +368,27 @@ int raft_engine_sm_write(raft_engine* e, int64_t g0, int64_t n, const raft_sm_he
 int raft_engine_sm_get(raft_engine* e, const int64_t* group, const int32_t* replica, const uint32_t* key,
                        raft_sm_value* out, int64_t n) {
     if (int rc = check_sm(e)) return rc;
-    if (n < 0) return raft_internal_fail(RAFT_EINVAL, "negative batch");
-    if (n > 0x7FFFFFFF) return raft_internal_fail(RAFT_EINVAL, "batch larger than 2^31 - 1 messages");
+    if (int rc = check_args(e, n, !group || !replica || !key || !out)) return rc;
     if (n == 0) return RAFT_OK;
-    if (!group || !replica || !key || !out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
-    // the host arrays through the client path's staging: page-locked (hst), one DMA to the
-    // device copies (cio); the records come back the same way
-    const size_t b_g = al256((size_t)n * 8), b_4 = al256((size_t)n * 4), b_out = (size_t)n * sizeof(raft_sm_value);
-    const size_t in_bytes = b_g + 2 * b_4;
+    const void* src[3] = {group, replica, key};
+    const size_t bytes[3] = {(size_t)n * 8, (size_t)n * 4, (size_t)n * 4};
+    Staged s;
+    if (int rc = stage_in(e, src, bytes, 3, (size_t)n * sizeof(raft_sm_value), s)) return rc;
     if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, GW_BYTES)) return rc;
-    if (int rc = raft_internal_grow_dev(e, &e->cio, &e->cio_bytes, in_bytes + al256(b_out))) return rc;
-    if (int rc = raft_internal_grow_host(e, &e->hst, &e->hst_bytes, in_bytes + al256(b_out))) return rc;
-    std::memcpy(e->hst, group, (size_t)n * 8);
-    std::memcpy(e->hst + b_g, replica, (size_t)n * 4);
-    std::memcpy(e->hst + b_g + b_4, key, (size_t)n * 4);
-    unsigned int* flags = (unsigned int*)e->cli;
-    HIP_TRY(hipMemsetAsync(flags, 0, GW_WORDS * 4, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->cio, e->hst, in_bytes, hipMemcpyHostToDevice, e->stream));
+    GetStatus st;
+    if (int rc = st.zero(e, e->cli)) return rc;
     sm_get_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
-        e->dp, e->sm_slots, heads_of(e), regs_of(e), (const int64_t*)e->cio, (const int32_t*)(e->cio + b_g),
-        (const uint32_t*)(e->cio + b_g + b_4), (int4*)(e->cio + in_bytes), (int)n, flags);
+        e->dp, e->sm_slots, sm_heads_of(e), sm_regs_of(e), (const int64_t*)(e->cio + s.off[0]),
+        (const int32_t*)(e->cio + s.off[1]), (const uint32_t*)(e->cio + s.off[2]), (int4*)(e->cio + s.out_off), (int)n,
+        st.dev);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(e->bflags_host, flags, GW_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->hst + in_bytes, e->cio + in_bytes, b_out, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->bflags_host[GW_RANGE])
+    if (int rc = stage_out_dma(e, s)) return rc;
+    if (int rc = st.fetch(e)) return rc;                                // (waits for the records too)
+    if (st.w[GW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a read's group or replica is outside the engine; nothing was filled");
-    std::memcpy(out, e->hst + in_bytes, b_out);
+    stage_out_copy(e, s, out);
     return RAFT_OK;
 }
 
@@ -438,7 +404,7 @@ int raft_engine_sm_check(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, 
     uint8_t* fl = flags ? (uint8_t*)e->aux + 8 : nullptr;
     unsigned long long h = 0;
     HIP_TRY(hipMemsetAsync(cnt, 0, 8, e->stream));
-    sm_check_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(e->dp, heads_of(e), g0, n, fl, cnt);
+    sm_check_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(e->dp, sm_heads_of(e), g0, n, fl, cnt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, e->stream));
     if (flags) HIP_TRY(hipMemcpyAsync(flags, fl, (size_t)n, hipMemcpyDeviceToHost, e->stream));

@@ -168,6 +168,82 @@ def test_dev_variants_equal_host_variants():
         assert a.digest() == b.digest()
 
 
+def test_host_variants_interleaved_share_one_staging():
+    """The host variants of propose, resolve, read begin, read serve and sm_get
+    back to back on one engine, n cycling through 1, 3, 300: every call lays
+    its arrays out differently in the same staging (300 crosses a block, and the
+    smaller n after it reuses the oversized buffers).  Each result equals the
+    device variant's on the same inputs (propose: on a second engine holding
+    the same state and logs; sm_get has none: the machine, read back).  A bad
+    group between the two cycles leaves the following calls unaffected."""
+    import torch
+    R, G, S = 3, 8, 4
+    kw = dict(R=R, G=G, seed=11, log_cap=300, **M.FLAT_MIX)
+    rng = np.random.default_rng(12)
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int32).reshape(-1)).to("cuda:0")
+
+    def out_of(n, dtype, call, rc=abi.RAFT_OK):            # a device variant's n 16-byte records, and nothing beyond
+        d = torch.zeros((n + 1) * 4, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        assert call(d.data_ptr()) == rc
+        raw = d.cpu().numpy()
+        assert not raw[-4:].any()
+        return raw[:-4].view(dtype)
+
+    with RaftEngine(abi.make_params(**kw)) as a, RaftEngine(abi.make_params(**kw)) as b:
+        a.sm_configure(S)
+        a.step(40, counters=False)
+        assert (a.leaders()["leader"] >= 0).any()
+        routed = 0
+        for k, n in enumerate((1, 3, 300, 1, 3, 300)):
+            if k == 3:                                     # the argument errors the API reports, mid-cycle
+                with pytest.raises(RaftError, match="outside"):
+                    a.propose([1, G, 2], [5, 6, 7])
+                with pytest.raises(RaftError, match="outside"):
+                    a.begin_reads([1, G, 2])
+                with pytest.raises(RaftError, match="outside"):
+                    a.sm_get([0, G, 1], [1, 2, 3])
+                a.step(10, counters=False)                 # the first cycle's proposals commit
+            a.sm_apply()
+            b.write_state(a.read_state())
+            b.write_log(*a.read_log())
+            groups = rng.integers(0, G, n, dtype=np.int64)
+            cmds = rng.integers(1, 2 ** 32, n, dtype=np.uint32)
+            keys = rng.integers(0, 2 ** 32, n, dtype=np.uint32)
+            dg, dc, dk = dev(groups), dev(cmds), dev(keys)
+            label = f"call {k}, n = {n}"
+            tk = a.propose(groups, cmds)
+            routed += int((tk["replica"] >= 0).sum())
+            same(out_of(n, abi.TICKET_DTYPE, lambda p: b.propose_dev(dg.data_ptr(), dc.data_ptr(), p, n)), tk,
+                 f"tickets, {label}")
+            dt = dev(tk)
+            same(out_of(n, abi.TICKET_STATE_DTYPE,
+                        lambda p: a.resolve_dev(dg.data_ptr(), dt.data_ptr(), dc.data_ptr(), p, n)),
+                 a.resolve(groups, tk, cmds), f"records, {label}")
+            rt = a.begin_reads(groups)
+            same(out_of(n, abi.READ_TICKET_DTYPE, lambda p: a.begin_reads_dev(dg.data_ptr(), p, n)), rt,
+                 f"read tickets, {label}")
+            drt = dev(rt)
+            # a NO_LEADER ticket names no replica: its record is INVALID and the call RAFT_EINVAL, every record filled
+            res = a.serve_reads(groups, rt, keys, check=False)
+            assert a.last_status == (abi.RAFT_EINVAL if (rt["status"] == abi.READ_NO_LEADER).any() else abi.RAFT_OK)
+            same(out_of(n, abi.READ_RESULT_DTYPE,
+                        lambda p: a.serve_reads_dev(dg.data_ptr(), drt.data_ptr(), dk.data_ptr(), p, n, check=False),
+                        a.last_status), res, f"read results, {label}")
+            ld, (heads, regs) = a.leaders(), a.sm_read()
+            r = ld["leader"][groups]
+            led = r >= 0
+            want = np.zeros(n, dtype=abi.SM_VALUE_DTYPE)
+            want["replica"] = r
+            want["value"][led] = regs[groups[led], r[led], keys[led] & (S - 1)]
+            want["applied"][led] = heads["applied"][groups[led], r[led]]
+            want["commit"][led] = ld["commit"][groups[led]]
+            same(a.sm_get(groups, keys), want, f"values, {label}")
+        assert routed > 0
+
+
 def test_arguments():
     R, G, cap = 3, 8, 16
     w, t, c = M.crafted(R, G, cap)
