@@ -840,6 +840,82 @@ int raft_read_serve_batch    (raft_engine* e, const int64_t* group, const raft_r
 int raft_read_serve_batch_dev(raft_engine* e, const int64_t* group, const raft_read_ticket* ticket, const uint32_t* key,
                               raft_read_result* out, int64_t n);
 
+/* ---- snapshot install: a lagging replica healed from its leader on the device -
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The reference has no counterpart: it has neither log compaction nor a
+ * snapshot.  The source is the Raft paper's §7 (InstallSnapshot).  The
+ * log_window ring already compacts physically; this is the other half, the way
+ * back for a replica whose missing entries have left the leader's window (or,
+ * on a flat log, one that would otherwise catch up one AppendEntries a step).
+ * One kernel between two step launches copies the leader's retained log, its
+ * machine and its commit point into the chosen replicas in HBM; nothing goes
+ * through the host.  The snapshot IS the leader's machine, so the call needs
+ * raft_engine_sm_configure.
+ *
+ * Per group of [g0, g0 + n):
+ * - The leader L is chosen by the read path's rule (raft_read_begin_batch): the
+ *   replica with role LEADER and the highest currentTerm, the lowest index
+ *   among equals.  Not raft_leader_info.leader.  T = currentTerm_L and hi =
+ *   clamp(min(commitIndex_L, lastIndex_L), 0, log_cap).
+ * - No replica is LEADER: the group counts in no_leader.  L's machine has
+ *   lost != 0 (it is not the fold of its log): the group counts in
+ *   leader_gapped.  Neither kind of group is changed.  Both are counted
+ *   whatever the mask says.
+ * - Replica f is installed when it is eligible (bit f of mask[j] for group
+ *   g0 + j; bits at or above R are ignored; a NULL mask makes every replica
+ *   eligible), f != L, currentTerm_f <= T (an eligible f != L with a higher
+ *   term counts in `ahead` and is skipped) and lastIndex_L - lastIndex_f >=
+ *   min_lag (min_lag 0: every such replica, even one level with L).
+ *
+ * An installed f, in terms of read_state / read_log / sm_read, with floor =
+ * max(0, physLen_L - log_window) on a ring and 0 on a flat log:
+ * - lastIndex_f = lastIndex_L, physLen_f = physLen_L, and slots [floor,
+ *   physLen_L) of f's row are copies of L's (slots_copied adds physLen_L -
+ *   floor); its other slots are unspecified beyond what read_log zeroes;
+ * - commitIndex_f = hi, currentTerm_f = T, votedFor_f kept if currentTerm_f was
+ *   T already, else -1;
+ * - the volatile state is what raft_engine_restart leaves: role FOLLOWER, flags
+ *   RAFT_FL_ARMED alone, phaseMs = retryMs = 0, electionMs a fresh draw (the
+ *   replica's RAFT_RNG_TIMER word at the engine's step index), rows next[f][*]
+ *   and match[f][*] = 0;
+ * - the leader's session towards it: next[L][f] = lastIndex_L + 1 and
+ *   match[L][f] = lastIndex_L, what the leader holds after f acknowledged
+ *   everything.  No other word of L changes;
+ * - the machine: f's head (applied, lost, hash) and registers are copies of L's;
+ * - lastApplied (the drain's cursor) is not touched: the drain's own lost /
+ *   regressed rules cover it.
+ * The engine's mirrors (the log-tail cache, the session rows' placement) end up
+ * as a write_state + write_log + sm_write of the same words would leave them,
+ * without the engine-wide cache rebuild.
+ *
+ * The call is the same in both protocol modes.  Promised in RAFT_MODE_TEXTBOOK
+ * without RAFT_RESTART_AMNESIA: the install equals what a lossless run of
+ * AppendEntries from L at term T would eventually produce, so
+ * RAFT_C_DUAL_LEADER_GROUPS, raft_engine_check_log_matching and
+ * raft_engine_sm_check stay clean.  In RAFT_MODE_REFERENCE it is defined but
+ * nothing is promised (ghost tails, Q4, Q9), as elsewhere.  Drops, partitions
+ * and the isolation word are not consulted: the install is a teleport, the same
+ * lossless instantaneous round as the read path's confirmation.
+ *
+ * Ordering is raft_engine_restart's: the engine stream, later step launches
+ * wait for it, it returns when its kernel has finished.  The _dev form takes
+ * the mask in DEVICE memory under the buffer rules of raft_*_batch_dev.
+ * RAFT_EINVAL: null engine or info, the machine not configured, min_lag < 0;
+ * RAFT_ERANGE: groups outside the engine.  n == 0 is RAFT_OK with a zeroed info. */
+typedef struct raft_install_info {   /* 64 bytes */
+    int64_t installed;      /* replicas installed */
+    int64_t slots_copied;   /* log slots copied into them */
+    int64_t no_leader;      /* groups of the range with no LEADER: nothing done */
+    int64_t leader_gapped;  /* groups whose leader's machine has lost != 0: nothing done */
+    int64_t ahead;          /* masked replicas with currentTerm > the leader's: skipped */
+    int64_t reserved[3];    /* 0 */
+} raft_install_info;
+int raft_engine_install_snapshot    (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_host,
+                                     int32_t min_lag, raft_install_info* info);
+int raft_engine_install_snapshot_dev(raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev,
+                                     int32_t min_lag, raft_install_info* info);
+
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages
  * to the same (group, dst) are applied in batch order.  Effects on the

@@ -241,6 +241,17 @@ RESTART_MAX_DOWN_STEPS = (1 << 23) - 1
 RNG_TIMER, RNG_RESTART = 1, 7
 
 
+class raft_install_info(C.Structure):
+    _fields_ = [("installed", C.c_int64), ("slots_copied", C.c_int64), ("no_leader", C.c_int64),
+                ("leader_gapped", C.c_int64), ("ahead", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+# raft_engine_install_snapshot*: the info as a numpy record (64 bytes, no padding)
+INSTALL_INFO_DTYPE = np.dtype([("installed", np.int64), ("slots_copied", np.int64), ("no_leader", np.int64),
+                               ("leader_gapped", np.int64), ("ahead", np.int64), ("reserved", np.int64, (3,))])
+INSTALL_INFO_FIELDS = ("installed", "slots_copied", "no_leader", "leader_gapped", "ahead")
+
+
 class raft_read_ticket(C.Structure):
     _fields_ = [("replica", C.c_int32), ("term", C.c_int32), ("read_index", C.c_int32), ("status", C.c_int32)]
 
@@ -415,6 +426,8 @@ def load_library(path: str | None = None):
         "raft_engine_restart": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
         "raft_engine_restart_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
         "raft_engine_restart_random": (C.c_int, [eng, I64, I64, C.c_uint32, I32, I32, P(raft_restart_info)]),
+        "raft_engine_install_snapshot": (C.c_int, [eng, I64, I64, C.c_void_p, I32, P(raft_install_info)]),
+        "raft_engine_install_snapshot_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, P(raft_install_info)]),
         "raft_read_begin_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
         "raft_read_begin_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
         "raft_read_serve_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
@@ -476,6 +489,7 @@ EXPORTED_SYMBOLS = [
     "raft_engine_sm_configure", "raft_engine_sm_apply", "raft_engine_sm_read", "raft_engine_sm_write",
     "raft_engine_sm_get", "raft_engine_sm_check",
     "raft_engine_restart", "raft_engine_restart_dev", "raft_engine_restart_random",
+    "raft_engine_install_snapshot", "raft_engine_install_snapshot_dev",
     "raft_read_begin_batch", "raft_read_begin_batch_dev", "raft_read_serve_batch", "raft_read_serve_batch_dev",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",

@@ -625,6 +625,48 @@ class RaftEngine:
                                                       C.byref(ri)), "raft_engine_restart_dev")
         return self._restart_info(ri)
 
+    # -- snapshot install (raft_engine_install_snapshot*) --------------------------
+    def install_snapshot(self, mask=None, *, g0: int = 0, n: int | None = None, min_lag: int = 0,
+                         device_mask: int | None = None) -> dict:
+        """Heal lagging replicas of groups [g0, g0 + n) from their group's newest
+        leader, on the device (engine.sm_configure first): an eligible replica
+        whose lastIndex is at least `min_lag` behind the leader's and whose term
+        is not above it gets the leader's retained log, commit point, term and
+        machine, comes back as a FOLLOWER with a fresh election timeout, and the
+        leader's session counts it as caught up.  `mask` (n bytes, bit r of
+        mask[j]: replica r of group g0 + j) or `device_mask` (the same bytes in
+        DEVICE memory, e.g. a torch uint8 tensor's data_ptr()) names the
+        eligible replicas; neither: every replica.  Returns installed,
+        slots_copied, no_leader, leader_gapped, ahead (include/raft_engine.h
+        raft_install_info)."""
+        if mask is not None and device_mask is not None:
+            raise ValueError("install_snapshot: at most one of mask and device_mask")
+        m = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
+                raise ValueError(f"install_snapshot: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
+            n = m.shape[0] if n is None else n
+            if m.shape[0] != n:
+                raise ValueError(f"install_snapshot: mask holds {m.shape[0]} groups, n is {n}")
+            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n), ("min_lag", min_lag)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"install_snapshot: {name} must be an integer, not {v!r}")
+        if min_lag < 0:
+            raise ValueError("install_snapshot: min_lag must not be negative")
+        ii = abi.raft_install_info()
+        if device_mask is not None:
+            rc = self._lib.raft_engine_install_snapshot_dev(self._h, int(g0), int(n), C.c_void_p(int(device_mask)),
+                                                            int(min_lag), C.byref(ii))
+        else:
+            rc = self._lib.raft_engine_install_snapshot(self._h, int(g0), int(n),
+                                                        C.c_void_p(m.ctypes.data) if m is not None and m.size else None,
+                                                        int(min_lag), C.byref(ii))
+        self._check(rc, "raft_engine_install_snapshot")
+        return {k: int(getattr(ii, k)) for k in abi.INSTALL_INFO_FIELDS}
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

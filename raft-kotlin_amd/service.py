@@ -166,6 +166,14 @@ class RaftNode:
         entries() is empty and currentTerm is 0 afterwards."""
         return self.s.restart([self.group], [self.replica], amnesia=amnesia, replay=replay, down_steps=down_steps)
 
+    def install(self, min_lag: int = 0) -> dict:
+        """Bring this node up to its group's newest leader (RaftEngine.install_snapshot
+        with only this node eligible): the leader's retained log, commit point
+        and machine.  Nothing happens to the leader itself, to a node in a
+        higher term, or in a group without a leader; the info says which."""
+        return self.s.engine.install_snapshot(np.array([1 << self.replica], dtype=np.uint8), g0=self.group,
+                                              min_lag=min_lag)
+
     def machine(self) -> tuple:
         """This node's state machine: (head, registers) -- head a record of
         abi.SM_HEAD_DTYPE (applied, lost, hash), registers [slots] uint32."""
@@ -302,6 +310,22 @@ class RaftService:
         mask = np.zeros(int(g.max()) - g0 + 1, dtype=np.uint8)
         np.bitwise_or.at(mask, g - g0, (1 << r).astype(np.uint8))
         return self.engine.restart(mask, g0=g0, amnesia=amnesia, replay=replay, down_steps=down_steps)
+
+    # -- snapshot install (Raft paper §7; the reference has none) -----------------------------
+    def heal(self, min_lag: Optional[int] = None) -> dict:
+        """Bring every replica that fell far behind back from its group's newest
+        leader: one apply_committed, so that each leader's machine (the snapshot)
+        holds its whole committed prefix, then one install_snapshot of every
+        group.  min_lag: how many entries behind the leader's lastIndex a replica
+        must be; by default half a log_window on a ring (the replica is about
+        to lose the leader's window) and a quarter of log_cap on a flat log.
+        Returns the install's info; ``last_heal_apply`` keeps the apply's."""
+        e = self.engine
+        if min_lag is None:
+            W = int(e.p.log_window)
+            min_lag = W // 2 if W else e.cap // 4
+        self.last_heal_apply = self.apply_committed()
+        return e.install_snapshot(min_lag=min_lag)
 
     # -- the client path: /cmd/{command} (RaftServer.kt:87-88) with an answer ---
     def leader(self, group: int) -> Optional[RaftNode]:
