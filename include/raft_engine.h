@@ -916,6 +916,144 @@ int raft_engine_install_snapshot    (raft_engine* e, int64_t g0, int64_t n, cons
 int raft_engine_install_snapshot_dev(raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev,
                                      int32_t min_lag, raft_install_info* info);
 
+/* ---- leadership transfer: TimeoutNow on the device, with tickets -------------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The reference has no counterpart: its leader only ever loses leadership by
+ * timeout.  The source is Ongaro's thesis §3.10 (TimeoutNow), as etcd and
+ * hashicorp/raft ship it: before a planned restart (raft_engine_restart with
+ * down_steps) a replica hands its groups on, instead of leaving each of them
+ * leaderless for an election timeout.  A transfer is "the target's election
+ * timer fires now": the only word a call writes is the target's electionMs = 1,
+ * so phase T of the next step fires it, for any heartbeat period, and the
+ * election runs under the step's own rules.  Nothing else is written, neither
+ * on the leader nor in the sessions, and no engine-wide rebuild follows; the
+ * word has no mirror in the engine, so the state is what a write_state of the
+ * same word would leave.
+ *
+ * Transfer: message m asks group[m] to move its leadership to replica
+ * target[m], or with RAFT_TRANSFER_AUTO to the best-placed other replica.
+ * - `from` is the group's newest leader by the read path's rule
+ *   (raft_read_begin_batch): role LEADER, the highest currentTerm, the lowest
+ *   index among equals.
+ * - The ticket's status, first match wins:
+ *     INVALID      target outside -1..R-1: nothing was read or written  (-1, 0, -1)
+ *     NO_LEADER    no replica of the group is LEADER                     (-1, 0, -1)
+ *     SELF         target == from: nothing to do                         (from, T, -1)
+ *     BEHIND       the target's (lastIndex, last log term) differ from
+ *                  the leader's: the thesis's "caught up", read from HBM
+ *                  as the read path reads its heartbeat round (lossless
+ *                  and instantaneous), not from matchIndex               (from, T, -1)
+ *     BUSY         the target's role is not FOLLOWER, or its flags lack
+ *                  RAFT_FL_ARMED, or have RAFT_FL_ELECTING, RAFT_FL_BACKOFF
+ *                  or RAFT_FL_PENDING_RST (electing, a candidate, a stale
+ *                  leader of a lower term)                               (from, T, -1)
+ *     UNREACHABLE  the group's isolation word (RAFT_GROUP_EXTRA[0]) has
+ *                  steps left and names the target                       (from, T, -1)
+ *     SENT         the target's electionMs = 1                           (from, T, target)
+ *   With RAFT_TRANSFER_AUTO the replicas other than `from` are judged by the
+ *   same three rules in the order from + 1, from + 2, ... (mod R) and the first
+ *   that passes is the target: "caught up" already makes every candidate's log
+ *   the leader's, and the cyclic order spreads leaders instead of piling them
+ *   on replica 0.  None passes (always so at R = 1): NO_TARGET (from, T, -1).
+ * - Several messages for one group are each judged against the state before
+ *   the call and honoured on their own: the same target twice is idempotent,
+ *   two different targets fire two timers and the step's election decides.
+ * - A group outside the engine fails the whole batch with RAFT_ERANGE before
+ *   anything is written, as raft_read_begin_batch does.  n == 0 is RAFT_OK.
+ *   n < 2^31.  RAFT_EINVAL: null engine, n < 0, a null buffer with n > 0.
+ * - It reads no log slot, so every log layout is served alike; the last log
+ *   term is the engine's log-tail cache, rebuilt first where a write_state /
+ *   write_log left it stale, as the handler batches do.
+ *
+ * Resolve: what became of ticket[m] of group[m].  Every record is filled; first
+ * match wins:
+ *   INVALID     the group is outside the engine, or a SENT ticket's from or
+ *               target is outside 0..R-1; nothing is read          (leader -1, term 0)
+ *   NONE        the ticket's status is not SENT                    (leader -1, term 0)
+ *   COMPLETED   the target is LEADER in a term above the ticket's  (target, its term)
+ *   SUPERSEDED  another replica is: the newest of them             (that replica, its term)
+ *   PENDING     no replica is LEADER in a term above the ticket's  (leader -1, term 0)
+ * Read-only.  Returns RAFT_ERANGE if any group was out of range, otherwise
+ * RAFT_EINVAL if any SENT ticket had a bad from or target (also: null engine,
+ * n < 0 or n >= 2^31, a null buffer with n > 0, and then nothing is filled),
+ * otherwise RAFT_OK.
+ *
+ * Evacuate, the range form for a planned restart: for each group of [g0, g0 + n)
+ * whose newest leader `from` has its bit set in mask[j] (the layout of
+ * raft_engine_restart's mask; bits at or above R are ignored), the AUTO rule
+ * with the masked replicas excluded as targets.  Groups led from outside the
+ * mask, and groups without a leader, are untouched.  There is no ticket (a
+ * caller that wants tickets uses the batch form); the info counts groups:
+ * `led` from inside the mask, of those `sent` and `no_target` (led = sent +
+ * no_target), and of the no_target groups `behind`, those with an unmasked
+ * replica refused as BEHIND, and `busy`, those with one refused as BUSY or
+ * UNREACHABLE (a group may count in both, or in neither when every other
+ * replica is masked).
+ * RAFT_EINVAL: null engine or info, a null mask with n > 0; RAFT_ERANGE: groups
+ * outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Both protocol modes.  In RAFT_MODE_REFERENCE the effect is whatever the
+ * reference does when that timer fires.  Promised in RAFT_MODE_TEXTBOOK with a
+ * flat log and no RAFT_RESTART_AMNESIA: a transfer is a timeout, which Raft
+ * tolerates at any moment, so Election Safety is untouched --
+ * RAFT_C_DUAL_LEADER_GROUPS, raft_engine_check_log_matching and
+ * raft_engine_sm_check stay at 0.  Not promised: that the target wins.  The old
+ * leader goes on accepting proposals until it hears of the new term; one that
+ * lands between the call and the next step makes the target's log shorter than
+ * the leader's, and its win then depends on the other followers' logs.  That is
+ * safe; the ticket says PENDING or SUPERSEDED and the caller transfers again.
+ *
+ * Ordering is raft_engine_restart's: each call runs on the engine stream, sees
+ * every step enqueued before it, later step launches wait for it, and it
+ * returns when its kernel has finished.  The _dev forms take DEVICE pointers
+ * under the buffer rules of raft_*_batch_dev; ticket and out must be 16-byte
+ * aligned. */
+#define RAFT_TRANSFER_AUTO       (-1)  /* target: the best-placed other replica (rule above) */
+#define RAFT_TRANSFER_SENT        0  /* the target's timer was set to fire in the next step */
+#define RAFT_TRANSFER_NO_LEADER   1  /* no replica of the group is LEADER */
+#define RAFT_TRANSFER_SELF        2  /* the target already is the group's newest leader: nothing to do */
+#define RAFT_TRANSFER_BEHIND      3  /* the target's log is not the leader's (last index or last term differ) */
+#define RAFT_TRANSFER_BUSY        4  /* the target is not an idle, armed FOLLOWER (electing, candidate, a stale leader) */
+#define RAFT_TRANSFER_UNREACHABLE 5  /* the group's isolation word is running and names the target */
+#define RAFT_TRANSFER_NO_TARGET   6  /* AUTO / evacuate: no replica qualifies */
+#define RAFT_TRANSFER_INVALID     7  /* target outside -1..R-1: nothing was read or written */
+typedef struct raft_transfer_ticket {  /* 16 bytes */
+    int32_t from;     /* the leader the transfer left (-1: none) */
+    int32_t term;     /* its term at the call */
+    int32_t target;   /* the replica whose timer was set (AUTO resolved; -1: none) */
+    int32_t status;   /* RAFT_TRANSFER_SENT ... RAFT_TRANSFER_INVALID */
+} raft_transfer_ticket;
+int raft_transfer_batch    (raft_engine* e, const int64_t* group, const int32_t* target, raft_transfer_ticket* ticket,
+                            int64_t n);
+int raft_transfer_batch_dev(raft_engine* e, const int64_t* group, const int32_t* target, raft_transfer_ticket* ticket,
+                            int64_t n);
+#define RAFT_TRANSFER_COMPLETED  0  /* the target is LEADER in a term above the ticket's */
+#define RAFT_TRANSFER_PENDING    1  /* no replica is LEADER in a term above the ticket's */
+#define RAFT_TRANSFER_SUPERSEDED 2  /* another replica is */
+#define RAFT_TRANSFER_NONE       3  /* the ticket's status was not SENT */
+/* RAFT_TRANSFER_INVALID as above: group, from or target outside the engine */
+typedef struct raft_transfer_state {   /* 16 bytes */
+    int32_t status;   /* one of the five above */
+    int32_t leader;   /* COMPLETED / SUPERSEDED: the LEADER found, else -1 */
+    int32_t term;     /* its term, else 0 */
+    int32_t reserved; /* 0 */
+} raft_transfer_state;
+int raft_engine_resolve_transfers    (raft_engine* e, const int64_t* group, const raft_transfer_ticket* ticket,
+                                      raft_transfer_state* out, int64_t n);
+int raft_engine_resolve_transfers_dev(raft_engine* e, const int64_t* group, const raft_transfer_ticket* ticket,
+                                      raft_transfer_state* out, int64_t n);
+typedef struct raft_evacuate_info {    /* 64 bytes */
+    int64_t led;          /* groups of the range whose newest leader is in the mask */
+    int64_t sent;         /* of those, the groups in which a timer was set */
+    int64_t no_target;    /* of those, the groups in which no replica qualified */
+    int64_t behind;       /* of no_target, the groups with an unmasked replica refused as BEHIND */
+    int64_t busy;         /* of no_target, the groups with one refused as BUSY or UNREACHABLE */
+    int64_t reserved[3];  /* 0 */
+} raft_evacuate_info;
+int raft_engine_evacuate    (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_host, raft_evacuate_info* info);
+int raft_engine_evacuate_dev(raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev, raft_evacuate_info* info);
+
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages
  * to the same (group, dst) are applied in batch order.  Effects on the

@@ -270,6 +270,32 @@ READ_SERVED, READ_BEHIND, READ_GAPPED, READ_NO_QUORUM, READ_DEPOSED, READ_NONE, 
 READ_STATUS_NAMES = ["SERVED", "BEHIND", "GAPPED", "NO_QUORUM", "DEPOSED", "NONE", "INVALID"]
 
 
+class raft_transfer_ticket(C.Structure):
+    _fields_ = [("from", C.c_int32), ("term", C.c_int32), ("target", C.c_int32), ("status", C.c_int32)]
+
+
+class raft_transfer_state(C.Structure):
+    _fields_ = [("status", C.c_int32), ("leader", C.c_int32), ("term", C.c_int32), ("reserved", C.c_int32)]
+
+
+class raft_evacuate_info(C.Structure):
+    _fields_ = [("led", C.c_int64), ("sent", C.c_int64), ("no_target", C.c_int64), ("behind", C.c_int64),
+                ("busy", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+# leadership transfer: the records as numpy records (16 bytes each, no padding), raft_transfer_ticket.status and
+# raft_transfer_state.status (RAFT_TRANSFER_*)
+TRANSFER_TICKET_DTYPE = np.dtype([("from", np.int32), ("term", np.int32), ("target", np.int32), ("status", np.int32)])
+TRANSFER_STATE_DTYPE = np.dtype([("status", np.int32), ("leader", np.int32), ("term", np.int32), ("reserved", np.int32)])
+TRANSFER_AUTO = -1
+(TRANSFER_SENT, TRANSFER_NO_LEADER, TRANSFER_SELF, TRANSFER_BEHIND, TRANSFER_BUSY, TRANSFER_UNREACHABLE,
+ TRANSFER_NO_TARGET, TRANSFER_INVALID) = range(8)
+TRANSFER_TICKET_STATUS_NAMES = ["SENT", "NO_LEADER", "SELF", "BEHIND", "BUSY", "UNREACHABLE", "NO_TARGET", "INVALID"]
+TRANSFER_COMPLETED, TRANSFER_PENDING, TRANSFER_SUPERSEDED, TRANSFER_NONE = 0, 1, 2, 3
+TRANSFER_STATE_NAMES = {0: "COMPLETED", 1: "PENDING", 2: "SUPERSEDED", 3: "NONE", 7: "INVALID"}
+EVACUATE_INFO_FIELDS = ("led", "sent", "no_target", "behind", "busy")
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -432,6 +458,12 @@ def load_library(path: str | None = None):
         "raft_read_begin_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
         "raft_read_serve_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_read_serve_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_transfer_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_transfer_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_resolve_transfers": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_resolve_transfers_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_evacuate": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
+        "raft_engine_evacuate_dev": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -491,6 +523,8 @@ EXPORTED_SYMBOLS = [
     "raft_engine_restart", "raft_engine_restart_dev", "raft_engine_restart_random",
     "raft_engine_install_snapshot", "raft_engine_install_snapshot_dev",
     "raft_read_begin_batch", "raft_read_begin_batch_dev", "raft_read_serve_batch", "raft_read_serve_batch_dev",
+    "raft_transfer_batch", "raft_transfer_batch_dev", "raft_engine_resolve_transfers",
+    "raft_engine_resolve_transfers_dev", "raft_engine_evacuate", "raft_engine_evacuate_dev",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

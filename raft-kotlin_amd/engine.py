@@ -667,6 +667,95 @@ class RaftEngine:
         self._check(rc, "raft_engine_install_snapshot")
         return {k: int(getattr(ii, k)) for k in abi.INSTALL_INFO_FIELDS}
 
+    # -- leadership transfer (raft_transfer_batch*, raft_engine_resolve_transfers*, raft_engine_evacuate*) ----
+    def transfer(self, groups, targets=None) -> np.ndarray:
+        """raft_transfer_batch: ask groups[m] to move its leadership to replica
+        targets[m] (abi.TRANSFER_AUTO, or targets=None: the first caught-up idle
+        follower after the leader, cyclically).  The target's election timer is
+        set to fire in the next step; nothing else is written.  Returns
+        abi.TRANSFER_TICKET_DTYPE tickets (from: the group's newest leader, its
+        term, target, status = abi.TRANSFER_SENT ... TRANSFER_INVALID)."""
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        t = np.full(g.shape, abi.TRANSFER_AUTO, dtype=np.int32) if targets is None else \
+            np.ascontiguousarray(targets, dtype=np.int32)
+        if g.ndim != 1 or t.shape != g.shape:
+            raise ValueError(f"transfer: groups {g.shape} and targets {t.shape} must be 1-D and of one length")
+        tk = np.zeros(g.shape[0], dtype=abi.TRANSFER_TICKET_DTYPE)
+        self._check(self._lib.raft_transfer_batch(self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data),
+                                                  C.c_void_p(tk.ctypes.data), g.shape[0]), "raft_transfer_batch")
+        return tk
+
+    def transfer_dev(self, group_ptr: int, target_ptr: int, ticket_ptr: int, n: int,
+                     after_stream: int | None = None) -> int:
+        """raft_transfer_batch_dev: DEVICE pointers to n int64 groups, int32
+        targets and 16-byte tickets (16-byte aligned), e.g. torch tensors'
+        data_ptr(); returns RAFT_OK once the batch finished."""
+        if ticket_ptr % 16:
+            raise ValueError("transfer_dev: the ticket buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_transfer_batch_dev(self._h, group_ptr, target_ptr, ticket_ptr, int(n)),
+                                   "raft_transfer_batch_dev", ())
+
+    def resolve_transfers(self, groups, tickets, check: bool = True) -> np.ndarray:
+        """raft_engine_resolve_transfers: what became of each transfer ticket, as
+        abi.TRANSFER_STATE_DTYPE records (status = abi.TRANSFER_COMPLETED /
+        TRANSFER_PENDING / TRANSFER_SUPERSEDED / TRANSFER_NONE / TRANSFER_INVALID,
+        the leader found and its term).  Read-only.  With check=False
+        RAFT_ERANGE / RAFT_EINVAL (some record is INVALID) are not raised:
+        ``last_status`` carries the code."""
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        t = np.ascontiguousarray(tickets)
+        if g.ndim != 1 or t.dtype != abi.TRANSFER_TICKET_DTYPE or t.ndim != 1 or t.shape[0] != g.shape[0]:
+            raise ValueError(f"resolve_transfers: tickets must be {g.shape[0]} records of abi.TRANSFER_TICKET_DTYPE")
+        out = np.zeros(g.shape[0], dtype=abi.TRANSFER_STATE_DTYPE)
+        self._client_status(self._lib.raft_engine_resolve_transfers(
+            self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(out.ctypes.data), g.shape[0]),
+            "raft_engine_resolve_transfers", () if check else (abi.RAFT_ERANGE, abi.RAFT_EINVAL))
+        return out
+
+    def resolve_transfers_dev(self, group_ptr: int, ticket_ptr: int, out_ptr: int, n: int,
+                              after_stream: int | None = None, check: bool = True) -> int:
+        """raft_engine_resolve_transfers_dev on DEVICE pointers (tickets and
+        records 16-byte aligned); returns the call's code (see resolve_transfers)."""
+        if ticket_ptr % 16 or out_ptr % 16:
+            raise ValueError("resolve_transfers_dev: the ticket and record buffers must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_engine_resolve_transfers_dev(self._h, group_ptr, ticket_ptr, out_ptr,
+                                                                               int(n)),
+                                   "raft_engine_resolve_transfers_dev", () if check else (abi.RAFT_ERANGE, abi.RAFT_EINVAL))
+
+    def evacuate(self, mask, g0: int = 0) -> dict:
+        """raft_engine_evacuate: for every group of [g0, g0 + len(mask)) whose
+        newest leader has its bit set in mask[j] (bit r: replica r), fire the
+        election timer of the first caught-up idle follower outside the mask
+        after that leader, cyclically -- the step before a planned restart of
+        the masked replicas.  Returns led, sent, no_target, behind, busy
+        (include/raft_engine.h raft_evacuate_info)."""
+        m = np.asarray(mask)
+        if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
+            raise ValueError(f"evacuate: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
+        if not isinstance(g0, (int, np.integer)) or isinstance(g0, bool):
+            raise ValueError(f"evacuate: g0 must be an integer, not {g0!r}")
+        m = np.ascontiguousarray(m, dtype=np.uint8)                   # the C side reads n bytes
+        ei = abi.raft_evacuate_info()
+        self._check(self._lib.raft_engine_evacuate(self._h, int(g0), m.shape[0], C.c_void_p(m.ctypes.data) if m.size else None,
+                                                   C.byref(ei)), "raft_engine_evacuate")
+        return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
+
+    def evacuate_dev(self, mask_ptr: int, n: int, g0: int = 0, after_stream: int | None = None) -> dict:
+        """evacuate with the mask in DEVICE memory (n bytes on this engine's GPU,
+        e.g. a torch uint8 tensor's data_ptr()); returns once the kernel finished."""
+        if n > 0 and not mask_ptr:
+            raise ValueError("evacuate_dev: a device mask is required")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        ei = abi.raft_evacuate_info()
+        self._check(self._lib.raft_engine_evacuate_dev(self._h, int(g0), int(n), C.c_void_p(mask_ptr or 0), C.byref(ei)),
+                    "raft_engine_evacuate_dev")
+        return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

@@ -21,6 +21,10 @@ argument meaning and error behaviour:
 * ``RaftService.read_linearizable``: the read a client can trust -- a ReadIndex
   ticket from the group's newest leader, confirmed against a majority of the
   group's terms before the register is read
+* ``RaftService.transfer_leadership`` / ``drain_node`` and ``RaftNode.step_down``:
+  leadership moved on purpose (Raft thesis §3.10; the reference's leader only
+  loses it by timeout) -- one group's, or every group a node leads before a
+  planned restart of that node
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -174,6 +178,19 @@ class RaftNode:
         return self.s.engine.install_snapshot(np.array([1 << self.replica], dtype=np.uint8), g0=self.group,
                                               min_lag=min_lag)
 
+    def step_down(self) -> str:
+        """Hand this node's leadership on to the best-placed other node of its
+        group (RaftService.transfer_leadership).  Returns the ticket's status
+        name: "SENT", or why nothing was sent; "NOT_LEADER", before any write,
+        when this node is not its group's newest leader."""
+        w = self.s.engine.read_state(self.group, 1)[0].reshape(-1)[:self.s.engine.R * abi.NUM_FIELDS]
+        w = w.reshape(self.s.engine.R, abi.NUM_FIELDS)
+        lead = [(-int(t), r) for r, (t, role) in enumerate(zip(w[:, abi.F_INDEX["term"]], w[:, abi.F_INDEX["role"]]))
+                if role == abi.LEADER]
+        if not lead or min(lead)[1] != self.replica:
+            return "NOT_LEADER"
+        return self.s.transfer_leadership(self.group)
+
     def machine(self) -> tuple:
         """This node's state machine: (head, registers) -- head a record of
         abi.SM_HEAD_DTYPE (applied, lost, hash), registers [slots] uint32."""
@@ -310,6 +327,35 @@ class RaftService:
         mask = np.zeros(int(g.max()) - g0 + 1, dtype=np.uint8)
         np.bitwise_or.at(mask, g - g0, (1 << r).astype(np.uint8))
         return self.engine.restart(mask, g0=g0, amnesia=amnesia, replay=replay, down_steps=down_steps)
+
+    # -- leadership transfer (Raft thesis §3.10; the reference's leader only loses leadership by timeout) ---
+    def transfer_leadership(self, group: int, to: Optional[int] = None) -> str:
+        """Move `group`'s leadership to node `to` (None: the first caught-up idle
+        follower after the leader, cyclically): its election timer fires in the
+        next step.  Returns the ticket's status name ("SENT", "NO_LEADER", "SELF",
+        "BEHIND", "BUSY", "UNREACHABLE", "NO_TARGET", "INVALID"); ``last_transfer``
+        keeps the ticket for RaftEngine.resolve_transfers."""
+        self.last_transfer = self.engine.transfer([group], [abi.TRANSFER_AUTO if to is None else to])
+        return abi.TRANSFER_TICKET_STATUS_NAMES[int(self.last_transfer["status"][0])]
+
+    def drain_node(self, replica: int, max_steps: int) -> int:
+        """Vacate node `replica` in every group before a planned restart of it:
+        while the leader directory (RaftEngine.leaders) names it in some group
+        and the budget lasts, one evacuate of that replica over every group and
+        one step.  Returns how many groups it still leads; ``last_drain`` keeps
+        the turns taken and each turn's evacuate info."""
+        e = self.engine
+        if not 0 <= replica < e.R:
+            raise IndexError(replica)
+        mask = np.full(e.G, 1 << replica, dtype=np.uint8)
+        infos = []
+        remaining = int((e.leaders()["leader"] == replica).sum())
+        while remaining and len(infos) < max_steps:
+            infos.append(e.evacuate(mask))
+            e.step(1)
+            remaining = int((e.leaders()["leader"] == replica).sum())
+        self.last_drain = {"turns": len(infos), "infos": infos}
+        return remaining
 
     # -- snapshot install (Raft paper §7; the reference has none) -----------------------------
     def heal(self, min_lag: Optional[int] = None) -> dict:
