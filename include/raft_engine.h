@@ -47,8 +47,11 @@ extern "C" {
  * (raft_engine_drain_committed*, raft_engine_read_applied / write_applied), the
  * client path (raft_engine_read_leaders, raft_propose_batch*, raft_engine_resolve_tickets*),
  * the replicated state machine (raft_engine_sm_*), replica restart
- * (raft_engine_restart*) and linearizable reads (raft_read_begin_batch*,
- * raft_read_serve_batch*) */
+ * (raft_engine_restart*), linearizable reads (raft_read_begin_batch*,
+ * raft_read_serve_batch*), snapshot install (raft_engine_install_snapshot*),
+ * leadership transfer (raft_transfer_batch*, raft_engine_resolve_transfers*,
+ * raft_engine_evacuate*) and leader no-op entries (raft_engine_append_noops*,
+ * raft_engine_sm_set_noop) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -759,8 +762,9 @@ int raft_engine_restart_random(raft_engine* e, int64_t g0, int64_t n, uint32_t p
  *     hi == 0 or log_L[hi - 1].term != T           (L, T, hi, TERM_UNCOMMITTED)
  *     otherwise                                    (L, T, hi, ISSUED)
  *   TERM_UNCOMMITTED: L has not yet committed an entry of its own term, so its
- *   commitIndex may lag behind acknowledged writes.  This engine has no no-op
- *   entry: a client command must commit first, and the client begins again.
+ *   commitIndex may lag behind acknowledged writes.  raft_engine_append_noops
+ *   (below) gives such a leader an entry of its own term; once that commits,
+ *   the client begins again.
  * - A group outside the engine fails the whole batch with RAFT_ERANGE before any
  *   ticket is written, as raft_propose_batch does.  n == 0 is RAFT_OK.  n < 2^31.
  *   RAFT_EWINDOW if any ticket is UNKNOWN, after filling every ticket.
@@ -1053,6 +1057,88 @@ typedef struct raft_evacuate_info {    /* 64 bytes */
 } raft_evacuate_info;
 int raft_engine_evacuate    (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_host, raft_evacuate_info* info);
 int raft_engine_evacuate_dev(raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev, raft_evacuate_info* info);
+
+/* ---- leader no-op entries: commit and read liveness after an election --------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The reference has no counterpart.  The source is Ongaro's thesis §3.6.2 and
+ * §6.4 step 1: a new leader appends an entry of its own term.  Without one, in
+ * RAFT_MODE_TEXTBOOK (whose commit rule counts current-term entries only) the
+ * entries of earlier terms stay uncommitted after a leader change until some
+ * client proposes again: an idle group answers raft_read_begin_batch with
+ * TERM_UNCOMMITTED for ever, and a raft_propose_batch ticket whose entry was
+ * replicated but not committed before a restart, a partition, a
+ * raft_transfer_batch or a raft_engine_evacuate stays PENDING.
+ *
+ * The call visits every group of [g0, g0 + n); nothing but the scalars comes
+ * from the host.  Per group:
+ * - L is the group's newest leader by the read path's rule
+ *   (raft_read_begin_batch): role LEADER, the highest currentTerm, the lowest
+ *   index among equals.  T = currentTerm_L.
+ * - The group's record, first match wins:
+ *     no replica is LEADER                       ticket (-1, -1, 0, NO_LEADER), ticket_cmd 0
+ *     lastIndex_L >= 1 and the term of L's last  nothing is appended: ticket (L, lastIndex_L - 1,
+ *       entry is T                                 T, CURRENT) names that entry, ticket_cmd its cmd
+ *     otherwise                                  appendCommand of `cmd` on L: the ticket and status
+ *                                                  raft_propose_batch writes for one message to L
+ *                                                  (ACCEPTED, reference mode's GHOSTED, LOG_FULL),
+ *                                                  ticket_cmd = cmd
+ *   So a second call in the same term appends nothing -- but for reference
+ *   mode's GHOSTED: that entry went to the physical end, the leader's visible
+ *   tail is still the stale slot, and the next call judges by it.
+ * - The effect on state, logs and the log-tail cache is exactly that of
+ *   raft_append_command_batch called with (group, L, cmd) on the groups that
+ *   appended; nothing else changes.  No log slot is read: the term of the last
+ *   entry is the engine's log-tail cache, rebuilt first where a write_state /
+ *   write_log left it stale, so every log layout is served alike.
+ * - ticket and ticket_cmd ([n] each, the record of group g0 + j at j) are both
+ *   given or both NULL.  (group, ticket, ticket_cmd) go to
+ *   raft_engine_resolve_tickets unchanged: it treats CURRENT like every status
+ *   other than NO_LEADER and LOG_FULL, as "stored".  COMMITTED there means "this
+ *   leader has committed an entry of its own term", which is exactly
+ *   raft_read_begin_batch's condition for ISSUED.
+ * - info counts groups: appended (lastIndex_L grew: ACCEPTED or GHOSTED), of
+ *   those ghosted, and current, no_leader, log_full; n = appended + current +
+ *   no_leader + log_full.
+ * - With a log_window, a RAFT_MODE_TEXTBOOK add below its replica's window
+ *   returns RAFT_EWINDOW after doing everything, as raft_propose_batch does.
+ * RAFT_EINVAL: null engine or info, only one of ticket and ticket_cmd, a _dev
+ * ticket buffer that is not 16-byte aligned; RAFT_ERANGE: groups outside the
+ * engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * The entry is an ordinary entry: the drain delivers it, and the caller knows
+ * the id it chose.  A state machine passes over it after
+ * raft_engine_sm_set_noop: while enabled, raft_engine_sm_apply treats an entry
+ * whose cmd equals `cmd` like any other for applied, lost and hash and writes
+ * no register for it.  Disabled is the default.  The setting is the engine's,
+ * not the machine's data: it may be set before raft_engine_sm_configure, and
+ * raft_engine_reset, sm_configure, sm_write, restart and snapshot install leave
+ * it alone.  RAFT_EINVAL: null engine.
+ *
+ * Both protocol modes.  Promised in RAFT_MODE_TEXTBOOK without
+ * RAFT_RESTART_AMNESIA: the call is a client command, which Raft tolerates at
+ * any moment, so RAFT_C_DUAL_LEADER_GROUPS, raft_engine_check_log_matching and
+ * raft_engine_sm_check stay at 0.
+ *
+ * Ordering is raft_engine_restart's: the call runs on the engine stream, sees
+ * every step enqueued before it, later step launches wait for it, and it
+ * returns when its kernel has finished.  The _dev form takes DEVICE pointers
+ * for the two arrays under the buffer rules of raft_*_batch_dev. */
+#define RAFT_PROPOSE_CURRENT   4  /* raft_engine_append_noops: nothing appended, the leader's last entry is
+                                     already of its own term; the ticket names that entry */
+typedef struct raft_noop_info {   /* 64 bytes */
+    int64_t appended;     /* groups whose leader got the entry (ACCEPTED or GHOSTED) */
+    int64_t current;      /* groups whose leader's last entry was of its own term already */
+    int64_t no_leader;    /* groups without a LEADER */
+    int64_t log_full;     /* groups whose leader's Log.add was refused for lack of capacity */
+    int64_t ghosted;      /* of appended, reference mode's GHOSTED */
+    int64_t reserved[3];  /* 0 */
+} raft_noop_info;
+int raft_engine_append_noops    (raft_engine* e, int64_t g0, int64_t n, uint32_t cmd, raft_ticket* ticket_host,
+                                 uint32_t* ticket_cmd_host, raft_noop_info* info);
+int raft_engine_append_noops_dev(raft_engine* e, int64_t g0, int64_t n, uint32_t cmd, raft_ticket* ticket_dev,
+                                 uint32_t* ticket_cmd_dev, raft_noop_info* info);
+int raft_engine_sm_set_noop(raft_engine* e, int enable, uint32_t cmd);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

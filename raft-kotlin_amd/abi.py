@@ -296,6 +296,22 @@ TRANSFER_STATE_NAMES = {0: "COMPLETED", 1: "PENDING", 2: "SUPERSEDED", 3: "NONE"
 EVACUATE_INFO_FIELDS = ("led", "sent", "no_target", "behind", "busy")
 
 
+class raft_noop_info(C.Structure):
+    _fields_ = [("appended", C.c_int64), ("current", C.c_int64), ("no_leader", C.c_int64), ("log_full", C.c_int64),
+                ("ghosted", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+# leader no-op entries (raft_engine_append_noops*): the ticket status of a group whose leader's last entry is of
+# its own term already (RAFT_PROPOSE_CURRENT, beside PROPOSE_* above), the info as a numpy record (64 bytes, no
+# padding)
+PROPOSE_CURRENT = 4
+NOOP_CMD = 0                 # RaftEngine.append_noops' default command id (any u32 the caller's commands never use)
+PROPOSE_STATUS_NAMES = ["ACCEPTED", "GHOSTED", "NO_LEADER", "LOG_FULL", "CURRENT"]
+NOOP_INFO_DTYPE = np.dtype([("appended", np.int64), ("current", np.int64), ("no_leader", np.int64),
+                            ("log_full", np.int64), ("ghosted", np.int64), ("reserved", np.int64, (3,))])
+NOOP_INFO_FIELDS = ("appended", "current", "no_leader", "log_full", "ghosted")
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -464,6 +480,10 @@ def load_library(path: str | None = None):
         "raft_engine_resolve_transfers_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
         "raft_engine_evacuate": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
         "raft_engine_evacuate_dev": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
+        "raft_engine_append_noops": (C.c_int, [eng, I64, I64, C.c_uint32, C.c_void_p, C.c_void_p, P(raft_noop_info)]),
+        "raft_engine_append_noops_dev": (C.c_int, [eng, I64, I64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   P(raft_noop_info)]),
+        "raft_engine_sm_set_noop": (C.c_int, [eng, C.c_int, C.c_uint32]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -525,6 +545,7 @@ EXPORTED_SYMBOLS = [
     "raft_read_begin_batch", "raft_read_begin_batch_dev", "raft_read_serve_batch", "raft_read_serve_batch_dev",
     "raft_transfer_batch", "raft_transfer_batch_dev", "raft_engine_resolve_transfers",
     "raft_engine_resolve_transfers_dev", "raft_engine_evacuate", "raft_engine_evacuate_dev",
+    "raft_engine_append_noops", "raft_engine_append_noops_dev", "raft_engine_sm_set_noop",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

@@ -7,6 +7,9 @@
 //   raft_sm.hip       the replicated state machine
 //   raft_fault.hip    replica restart
 //   raft_read.hip     linearizable reads
+//   raft_snapshot.hip snapshot install
+//   raft_transfer.hip leadership transfer
+//   raft_noop.hip     leader no-op entries
 // Device side: the HBM indexing helpers, a replica's quad load / store, the
 // leader lookups, the committed prefix.  Host side: the engine object and the
 // call plumbing of the entry points -- HIP_TRY, the argument checks, the
@@ -300,6 +303,10 @@ struct raft_engine {
     int sm_slots;
     hipEvent_t ev_sm[2];        // around the last apply kernel while sm_timing (scripts/sm_probe.py)
     bool sm_timing;
+    // raft_engine_sm_set_noop: while sm_noop_on an apply writes no register for an entry whose cmd is sm_noop_cmd.
+    // The engine's, not the machine's: off at create, and reset / sm_configure / sm_write leave it alone
+    bool sm_noop_on;
+    uint32_t sm_noop_cmd;
     int64_t* counters_dev;      // [K][STRIDE] scratch
     unsigned long long* accum;  // [K * NC] counter accumulators: sum + chunks done << 48 (zero between launches)
     // step-kernel event timing

@@ -73,9 +73,13 @@ struct Ent {
 
 // Wave w of the grid owns replicas [64 w, 64 w + 64) of the selection.  LDS per
 // wave: the powers P^0 .. P^64, then the 64 x S register words.
-template <int R>
+// NOOP (raft_engine_sm_set_noop enabled): an entry whose cmd is `noop` counts and
+// hashes like any other and writes no register; without it `noop` is unused and
+// the code is the plain apply's.
+template <int R, bool NOOP>
 __global__ __launch_bounds__(BLOCK) void sm_apply_kernel(DevParams p, Sel s, int logS, int4* __restrict__ heads,
-                                                         uint32_t* __restrict__ regs, unsigned long long* hdr) {
+                                                         uint32_t* __restrict__ regs, unsigned long long* hdr,
+                                                         uint32_t noop) {
     extern __shared__ unsigned long long sm_lds[];
     const int S = 1 << logS;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -180,8 +184,9 @@ __global__ __launch_bounds__(BLOCK) void sm_apply_kernel(DevParams p, Sel s, int
             uint64_t v = 0;
             if (live) {
                 v = sm_x(t.index, t.e.x, t.e.y) * pw[seg_hi - 1 - x];  // x(i, t, c) * P^(m - 1 - p)
-                atomicMax(&win[t.k * S + (int)(t.e.y & (uint32_t)(S - 1))],
-                          (unsigned long long)((uint64_t)(uint32_t)(t.index + 1) << 32 | t.e.y));
+                if (!NOOP || t.e.y != noop)
+                    atomicMax(&win[t.k * S + (int)(t.e.y & (uint32_t)(S - 1))],
+                              (unsigned long long)((uint64_t)(uint32_t)(t.index + 1) << 32 | t.e.y));
             }
             // segmented suffix sum: owners ascend with the lane, so "same owner d lanes on"
             // means the same part; the lanes past the last entry form a part of zeros
@@ -272,7 +277,12 @@ template <int R> struct ApplyL {
         const int64_t tiles = (s.N + 63) / 64;
         const unsigned grid = (unsigned)((tiles + wpb - 1) / wpb);
         const size_t lds = (size_t)wpb * (PW_WORDS + 64 * S) * 8;
-        sm_apply_kernel<R><<<grid, wpb * 64, lds, e->stream>>>(e->dp, s, logS, sm_heads_of(e), sm_regs_of(e), hdr);
+        if (e->sm_noop_on)
+            sm_apply_kernel<R, true><<<grid, wpb * 64, lds, e->stream>>>(e->dp, s, logS, sm_heads_of(e), sm_regs_of(e),
+                                                                         hdr, e->sm_noop_cmd);
+        else
+            sm_apply_kernel<R, false><<<grid, wpb * 64, lds, e->stream>>>(e->dp, s, logS, sm_heads_of(e),
+                                                                          sm_regs_of(e), hdr, 0u);
     }
 };
 
@@ -305,6 +315,13 @@ int raft_engine_sm_configure(raft_engine* e, int32_t slots) {
     }
     HIP_TRY(hipMemsetAsync(e->sm, 0, e->sm_bytes, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return RAFT_OK;
+}
+
+int raft_engine_sm_set_noop(raft_engine* e, int enable, uint32_t cmd) {
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    e->sm_noop_on = enable != 0;                     // read at the next apply's launch: nothing is enqueued
+    e->sm_noop_cmd = enable ? cmd : 0u;
     return RAFT_OK;
 }
 

@@ -756,6 +756,64 @@ class RaftEngine:
                     "raft_engine_evacuate_dev")
         return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
 
+    # -- leader no-op entries (raft_engine_append_noops*, raft_engine_sm_set_noop) -------------------------
+    def _noop_args(self, g0, n, cmd, what: str):
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n), ("cmd", cmd)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
+        if not 0 <= cmd <= 0xFFFFFFFF:
+            raise ValueError(f"{what}: cmd must be a u32 command id, not {cmd!r}")
+        return int(g0), int(n), int(cmd)
+
+    def append_noops(self, g0: int = 0, n: int | None = None, cmd: int = abi.NOOP_CMD, tickets: bool = False):
+        """raft_engine_append_noops: in every group of [g0, g0 + n) whose newest
+        leader's last entry is not of its own term (or whose log is empty),
+        appendCommand of `cmd` on that leader -- Raft's no-op entry, after which
+        the leader can commit what earlier terms left and serve linearizable
+        reads.  A second call in the same term appends nothing.  Returns the
+        info (appended, current, no_leader, log_full, ghosted; include/raft_engine.h
+        raft_noop_info), or with tickets=True (info, tickets, cmds): per group an
+        abi.TICKET_DTYPE ticket (status abi.PROPOSE_CURRENT where nothing was
+        appended: it names the leader's last entry) and the command id to
+        resolve it with.  RAFT_EWINDOW (a textbook add below a log_window) is not
+        raised: ``last_status`` carries the code."""
+        g0, n, cmd = self._noop_args(g0, n, cmd, "append_noops")
+        ni = abi.raft_noop_info()
+        t = np.zeros(max(n, 0), dtype=abi.TICKET_DTYPE) if tickets else None    # a bad range is the library's to refuse
+        c = np.zeros(max(n, 0), dtype=np.uint32) if tickets else None
+        self._client_status(self._lib.raft_engine_append_noops(
+            self._h, g0, n, cmd, C.c_void_p(t.ctypes.data) if tickets else None,
+            C.c_void_p(c.ctypes.data) if tickets else None, C.byref(ni)), "raft_engine_append_noops")
+        info = {k: int(getattr(ni, k)) for k in abi.NOOP_INFO_FIELDS}
+        return (info, t, c) if tickets else info
+
+    def append_noops_dev(self, ticket_ptr: int, cmd_ptr: int, g0: int = 0, n: int | None = None,
+                         cmd: int = abi.NOOP_CMD, after_stream: int | None = None) -> dict:
+        """append_noops with the tickets ([n] 16-byte records, 16-byte aligned)
+        and their command ids ([n] uint32) written to DEVICE memory, or both
+        pointers 0 for none; returns the info once the kernel finished."""
+        g0, n, cmd = self._noop_args(g0, n, cmd, "append_noops_dev")
+        if ticket_ptr % 16:
+            raise ValueError("append_noops_dev: the ticket buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        ni = abi.raft_noop_info()
+        self._client_status(self._lib.raft_engine_append_noops_dev(
+            self._h, g0, n, cmd, C.c_void_p(ticket_ptr or 0), C.c_void_p(cmd_ptr or 0), C.byref(ni)),
+            "raft_engine_append_noops_dev")
+        return {k: int(getattr(ni, k)) for k in abi.NOOP_INFO_FIELDS}
+
+    def sm_set_noop(self, cmd: int | None = abi.NOOP_CMD):
+        """raft_engine_sm_set_noop: from now on sm_apply counts and hashes an
+        entry whose command id is `cmd` like any other and writes no register
+        for it; cmd=None switches that off (the default).  The setting is the
+        engine's: it may be made before sm_configure and outlives reset."""
+        if cmd is not None and (isinstance(cmd, bool) or not isinstance(cmd, (int, np.integer))
+                                or not 0 <= cmd <= 0xFFFFFFFF):
+            raise ValueError(f"sm_set_noop: cmd must be a u32 command id or None, not {cmd!r}")
+        self._check(self._lib.raft_engine_sm_set_noop(self._h, int(cmd is not None), int(cmd or 0)), "sm_set_noop")
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

@@ -25,6 +25,9 @@ argument meaning and error behaviour:
   leadership moved on purpose (Raft thesis §3.10; the reference's leader only
   loses it by timeout) -- one group's, or every group a node leads before a
   planned restart of that node
+* ``RaftService.assert_leadership``: a new leader's no-op entry (Raft thesis
+  §3.6.2), so that an idle group commits what earlier terms left and serves
+  linearizable reads; ``entries()`` shows it as ``RaftService.NOOP_COMMAND``
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -270,7 +273,27 @@ class RaftService:
         return [(name(c), r, a, m) for c, r, a, m in
                 zip(v["value"].tolist(), v["replica"].tolist(), v["applied"].tolist(), v["commit"].tolist())]
 
-    def read_linearizable(self, groups, keys: List[str]) -> List[tuple]:
+    # -- leader no-op entries (Raft thesis §3.6.2; the reference has none) -------------------
+    NOOP_COMMAND = "raft:noop"          # the reserved command string of a leader's no-op entry
+
+    def assert_leadership(self, g0: int = 0, n: Optional[int] = None) -> dict:
+        """Give every leader of groups [g0, g0 + n) that has no entry of its own
+        term at the end of its log a no-op entry (RaftEngine.append_noops), so
+        that it can commit what earlier terms left behind and serve
+        linearizable reads after the next steps.  The entry's command is
+        NOOP_COMMAND, interned on first use (a service that never calls this
+        keeps its command ids); RaftNode.entries() and poll_committed show it
+        under that name, and a configured machine passes over it.  Returns the
+        info; ``last_noops`` keeps (groups, tickets, cmds) for RaftEngine.resolve."""
+        e = self.engine
+        cmd = self.commands.intern(self.NOOP_COMMAND)
+        if e.sm_slots:
+            e.sm_set_noop(cmd)
+        info, tk, cmds = e.append_noops(g0, n, cmd, tickets=True)
+        self.last_noops = (np.arange(g0, g0 + len(tk), dtype=np.int64), tk, cmds)
+        return info
+
+    def read_linearizable(self, groups, keys: List[str], assert_leadership: bool = False) -> List[tuple]:
         """The read a client can trust: per request (command, status name).
         One begin (a ReadIndex ticket from each group's newest leader), one
         serve of the tickets that were ISSUED (the leader confirmed against a
@@ -281,8 +304,13 @@ class RaftService:
         status is "SERVED", else None; the other statuses are "BEHIND" (still,
         after the apply), "GAPPED", "NO_QUORUM", "DEPOSED", or why no ticket was
         issued: "NO_LEADER", "TERM_UNCOMMITTED", "UNKNOWN" -- the client retries
-        after a step.  ``last_read`` keeps (tickets, records).  Keys as in read:
-        one that was never interned raises KeyError before any device call."""
+        after a step.  With assert_leadership=True the groups that answered
+        "TERM_UNCOMMITTED" are given their leader's no-op entry
+        (assert_leadership, one call per run of consecutive group ids) before
+        the call returns, so that the retry after the next steps is ISSUED; off,
+        the default, nothing is ever written.  ``last_read`` keeps (tickets,
+        records).  Keys as in read: one that was never interned raises KeyError
+        before any device call."""
         ids = [self.commands.lookup(k) for k in keys]
         unknown = [k for k, i in zip(keys, ids) if i is None]
         if unknown:
@@ -304,6 +332,10 @@ class RaftService:
                 cuts = np.nonzero(np.diff(ids_) != 1)[0] + 1
                 for run in np.split(ids_, cuts):
                     self.apply_committed(int(run[0]), len(run))
+        if assert_leadership:
+            ids_ = np.unique(g[tk["status"] == abi.READ_TERM_UNCOMMITTED])
+            for run in np.split(ids_, np.nonzero(np.diff(ids_) != 1)[0] + 1) if len(ids_) else ():
+                self.assert_leadership(int(run[0]), len(run))
         self.last_read = (tk, rec)
         name = self.commands.name
         return [(name(v), "SERVED") if s == abi.READ_SERVED else
