@@ -50,8 +50,9 @@ extern "C" {
  * (raft_engine_restart*), linearizable reads (raft_read_begin_batch*,
  * raft_read_serve_batch*), snapshot install (raft_engine_install_snapshot*),
  * leadership transfer (raft_transfer_batch*, raft_engine_resolve_transfers*,
- * raft_engine_evacuate*) and leader no-op entries (raft_engine_append_noops*,
- * raft_engine_sm_set_noop) */
+ * raft_engine_evacuate*), leader no-op entries (raft_engine_append_noops*,
+ * raft_engine_sm_set_noop) and the leader watch (raft_engine_poll_leaders*,
+ * raft_engine_read_watch / write_watch) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -1139,6 +1140,79 @@ int raft_engine_append_noops    (raft_engine* e, int64_t g0, int64_t n, uint32_t
 int raft_engine_append_noops_dev(raft_engine* e, int64_t g0, int64_t n, uint32_t cmd, raft_ticket* ticket_dev,
                                  uint32_t* ticket_cmd_dev, raft_noop_info* info);
 int raft_engine_sm_set_noop(raft_engine* e, int enable, uint32_t cmd);
+
+/* ---- the leader watch: leadership changes as a delta stream ------------------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * raft_engine_read_leaders returns 16 bytes for every group on every call and
+ * names the lowest-id LEADER, after an isolation often a deposed one.  A
+ * service that routes proposals and reads keeps a leader directory and needs
+ * only the changes (etcd's SoftState in a Ready, TiKV's role observer): a poll
+ * returns one record per group whose leader or term changed since the watch
+ * last reported that group.  The reference has no counterpart.
+ *
+ * - The engine keeps one `seen` pair (leader, term) per group, 8 bytes, in an
+ *   array of its own, as it does for lastApplied: it is not part of read_state
+ *   / write_state or of the digest, and the step kernel and every other call
+ *   never touch it.  It is allocated and set to (-1, 0) at the first call of
+ *   this section that needs it, raft_engine_reset sets it back to (-1, 0), it
+ *   counts in raft_engine_device_bytes and raft_engine_trim_staging keeps it.
+ * - A group's current leader is its newest leader by raft_read_begin_batch's
+ *   rule: role LEADER, the highest currentTerm, the lowest index among equals,
+ *   with that replica's currentTerm; (-1, 0) when no replica is LEADER.
+ *   Deliberately not raft_leader_info.leader: a deposed leader at a lower index
+ *   must not shadow its successor in a routing table.
+ * - A group of [g0, g0 + n) is changed when its current (leader, term) differs
+ *   from `seen` in either word.  Its record carries both pairs.  The four kinds
+ *   partition the changed groups: gained (prev_leader == -1, leader >= 0), lost
+ *   (prev_leader >= 0, leader == -1), moved (both >= 0, different replicas),
+ *   reterm (the same replica, another term).
+ * - Records come in ascending group order, identical from run to run.  When
+ *   more groups changed than max_events, exactly the first max_events of that
+ *   order are written, `seen` advances only for the groups that were written
+ *   and `pending` counts the rest: with no step in between, successive polls
+ *   concatenated equal one poll with enough room.  The kind counts and
+ *   `leaderless` describe the whole range at the call, not only what was
+ *   delivered.  out == NULL with max_events == 0 is a peek: nothing is stored,
+ *   not even `seen`.
+ * RAFT_EINVAL: null engine or info, max_events < 0, out == NULL with
+ * max_events > 0, a _dev buffer that is not 8-byte aligned; RAFT_ERANGE:
+ * groups outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Both protocol modes and every log layout: no log slot is read.  Nothing about
+ * Raft safety is promised or needed; the call reports role words.
+ *
+ * Ordering is raft_engine_drain_committed's: the call runs on the engine
+ * stream, sees every step enqueued before it, and later step launches wait for
+ * it.  The host variant returns after the copy; the _dev variant (out: a DEVICE
+ * pointer to max_events records; info stays a host pointer) returns after its
+ * kernels finished. */
+typedef struct raft_leader_event {   /* 24 bytes */
+    int64_t group;        /* engine-local group index */
+    int32_t leader;       /* the group's newest leader now, -1 if none */
+    int32_t term;         /* its currentTerm, 0 if none */
+    int32_t prev_leader;  /* what the watch last reported for the group (-1, 0 before the first report) */
+    int32_t prev_term;
+} raft_leader_event;
+typedef struct raft_watch_info {     /* 64 bytes */
+    int64_t delivered;    /* events written to out */
+    int64_t pending;      /* changed groups left for lack of room (all of them, in a peek) */
+    int64_t gained;       /* of the changed groups (delivered + pending): prev_leader == -1, leader >= 0 */
+    int64_t lost;         /*   prev_leader >= 0, leader == -1 */
+    int64_t moved;        /*   both >= 0 and different replicas */
+    int64_t reterm;       /*   the same replica, another term */
+    int64_t leaderless;   /* groups of the range with no LEADER now, changed or not */
+    int64_t reserved;     /* 0 */
+} raft_watch_info;
+int raft_engine_poll_leaders    (raft_engine* e, int64_t g0, int64_t n, raft_leader_event* out_host,
+                                 int64_t max_events, raft_watch_info* info);
+int raft_engine_poll_leaders_dev(raft_engine* e, int64_t g0, int64_t n, raft_leader_event* out_dev,
+                                 int64_t max_events, raft_watch_info* info);
+/* `seen` of groups [g0, g0 + n): [n][2] int32 (leader, term).  write_watch
+ * resumes a consumer: every leader in -1..R-1 and every term >= 0, a leader of
+ * -1 with term 0 only; anything else is RAFT_EINVAL and nothing is stored. */
+int raft_engine_read_watch (raft_engine* e, int64_t g0, int64_t n, int32_t* out);
+int raft_engine_write_watch(raft_engine* e, int64_t g0, int64_t n, const int32_t* in);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

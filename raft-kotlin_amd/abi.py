@@ -312,6 +312,27 @@ NOOP_INFO_DTYPE = np.dtype([("appended", np.int64), ("current", np.int64), ("no_
 NOOP_INFO_FIELDS = ("appended", "current", "no_leader", "log_full", "ghosted")
 
 
+class raft_leader_event(C.Structure):
+    _fields_ = [("group", C.c_int64), ("leader", C.c_int32), ("term", C.c_int32), ("prev_leader", C.c_int32),
+                ("prev_term", C.c_int32)]
+
+
+class raft_watch_info(C.Structure):
+    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("gained", C.c_int64), ("lost", C.c_int64),
+                ("moved", C.c_int64), ("reterm", C.c_int64), ("leaderless", C.c_int64), ("reserved", C.c_int64)]
+
+
+# the leader watch (raft_engine_poll_leaders*): raft_leader_event as a numpy record (24 bytes, no padding), the
+# info as one (64 bytes), a `seen` pair before the first report
+EVENT_DTYPE = np.dtype([("group", np.int64), ("leader", np.int32), ("term", np.int32), ("prev_leader", np.int32),
+                        ("prev_term", np.int32)])
+WATCH_INFO_DTYPE = np.dtype([("delivered", np.int64), ("pending", np.int64), ("gained", np.int64), ("lost", np.int64),
+                             ("moved", np.int64), ("reterm", np.int64), ("leaderless", np.int64),
+                             ("reserved", np.int64)])
+WATCH_INFO_FIELDS = ("delivered", "pending", "gained", "lost", "moved", "reterm", "leaderless")
+WATCH_UNSEEN = (-1, 0)
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -484,6 +505,10 @@ def load_library(path: str | None = None):
         "raft_engine_append_noops_dev": (C.c_int, [eng, I64, I64, C.c_uint32, C.c_void_p, C.c_void_p,
                                                    P(raft_noop_info)]),
         "raft_engine_sm_set_noop": (C.c_int, [eng, C.c_int, C.c_uint32]),
+        "raft_engine_poll_leaders": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_watch_info)]),
+        "raft_engine_poll_leaders_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_watch_info)]),
+        "raft_engine_read_watch": (C.c_int, [eng, I64, I64, P(I32)]),
+        "raft_engine_write_watch": (C.c_int, [eng, I64, I64, P(I32)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -546,6 +571,7 @@ EXPORTED_SYMBOLS = [
     "raft_transfer_batch", "raft_transfer_batch_dev", "raft_engine_resolve_transfers",
     "raft_engine_resolve_transfers_dev", "raft_engine_evacuate", "raft_engine_evacuate_dev",
     "raft_engine_append_noops", "raft_engine_append_noops_dev", "raft_engine_sm_set_noop",
+    "raft_engine_poll_leaders", "raft_engine_poll_leaders_dev", "raft_engine_read_watch", "raft_engine_write_watch",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

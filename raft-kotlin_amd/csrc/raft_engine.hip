@@ -1211,6 +1211,8 @@ int raft_engine_create(const raft_params* p, int device, raft_engine** out) {
     e->sm_slots = 0;
     e->ev_sm[0] = e->ev_sm[1] = nullptr;
     e->sm_timing = false;
+    e->watch = nullptr;
+    e->watch_bytes = 0;
     e->hpart = nullptr;
     e->hpart_bytes = 0;
     e->device = device;
@@ -1394,6 +1396,7 @@ int raft_engine_destroy(raft_engine* e) {
     if (e->cli) (void)hipFree(e->cli);
     if (e->cio) (void)hipFree(e->cio);
     if (e->sm) (void)hipFree(e->sm);
+    if (e->watch) (void)hipFree(e->watch);
     for (hipEvent_t x : e->ev_drain)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_sm)
@@ -1651,6 +1654,7 @@ int raft_engine_reset(raft_engine* e) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(e->applied, 0, e->applied_bytes, e->stream));   // nothing delivered yet
     if (e->sm) HIP_TRY(hipMemsetAsync(e->sm, 0, e->sm_bytes, e->stream));  // a configured machine: nothing applied yet
+    if (int rc = raft_internal_watch_reset(e)) return rc;                  // a leader watch in use: nothing reported yet
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->bflags_host[8] = 0u;                // the step kernel's status word
     e->t = 0;
@@ -1692,7 +1696,7 @@ int raft_engine_set_step_index(raft_engine* e, int64_t t) {
 }
 int64_t raft_engine_device_bytes(raft_engine* e) {
     return e ? (int64_t)(e->bytes + e->bst_bytes + e->bio_bytes + e->aux_bytes + e->hpart_bytes + e->applied_bytes +
-                         e->apl_bytes + e->apo_bytes + e->cli_bytes + e->cio_bytes + e->sm_bytes)
+                         e->apl_bytes + e->apo_bytes + e->cli_bytes + e->cio_bytes + e->sm_bytes + e->watch_bytes)
              : -1;
 }
 int raft_engine_trim_staging(raft_engine* e) {

@@ -10,6 +10,7 @@
 //   raft_snapshot.hip snapshot install
 //   raft_transfer.hip leadership transfer
 //   raft_noop.hip     leader no-op entries
+//   raft_watch.hip    the leader watch
 // Device side: the HBM indexing helpers, a replica's quad load / store, the
 // leader lookups, the committed prefix.  Host side: the engine object and the
 // call plumbing of the entry points -- HIP_TRY, the argument checks, the
@@ -35,6 +36,9 @@ extern "C" int raft_internal_grow_host(raft_engine* e, char** buf, size_t* have,
 // raft_engine.hip: enqueue the log-tail cache's rebuild on the engine stream
 // if a host write left it stale (cache_valid false)
 void raft_internal_ensure_cache(raft_engine* e);
+// raft_watch.hip: enqueue "nothing reported yet" for the leader watch on the
+// engine stream, if the watch is allocated (raft_engine_reset)
+int raft_internal_watch_reset(raft_engine* e);
 
 #define HIP_TRY(expr)                                                                                    \
     do {                                                                                                 \
@@ -307,6 +311,10 @@ struct raft_engine {
     // The engine's, not the machine's: off at create, and reset / sm_configure / sm_write leave it alone
     bool sm_noop_on;
     uint32_t sm_noop_cmd;
+    // the leader watch (raft_watch.hip): what it last reported per group [G] (leader, term), an allocation of
+    // its own like lastApplied's; nullptr until the first call that needs it.  Not staging: trim_staging keeps it
+    int2* watch;
+    size_t watch_bytes;
     int64_t* counters_dev;      // [K][STRIDE] scratch
     unsigned long long* accum;  // [K * NC] counter accumulators: sum + chunks done << 48 (zero between launches)
     // step-kernel event timing

@@ -814,6 +814,78 @@ class RaftEngine:
             raise ValueError(f"sm_set_noop: cmd must be a u32 command id or None, not {cmd!r}")
         self._check(self._lib.raft_engine_sm_set_noop(self._h, int(cmd is not None), int(cmd or 0)), "sm_set_noop")
 
+    # -- the leader watch (raft_engine_poll_leaders*, raft_engine_read_watch / write_watch) -----------------
+    def _watch_args(self, g0, n, max_events, what: str):
+        """The poll's arguments, checked before any library call."""
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
+        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
+                                       or max_events < 0):
+            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
+        return int(g0), int(n)
+
+    def _poll(self, fn, g0, n, out_ptr, room, what: str) -> dict:
+        wi = abi.raft_watch_info()
+        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(wi)), what)
+        return {k: int(getattr(wi, k)) for k in abi.WATCH_INFO_FIELDS}
+
+    def poll_leaders(self, g0: int = 0, n: int | None = None, max_events: int | None = None, peek: bool = False):
+        """raft_engine_poll_leaders: the groups of [g0, g0 + n) whose newest
+        leader (role LEADER, the highest currentTerm, the lowest index among
+        equals) or its term changed since the watch last reported them:
+        (info, events).  events is a numpy array of abi.EVENT_DTYPE (group,
+        leader, term, prev_leader, prev_term; -1 and 0 where there is none) in
+        ascending group order, at most max_events of them (None: as many as
+        there are -- a peek sizes the buffer); the watch advances for the
+        groups that were returned.  peek=True stores nothing and returns no
+        event.  info: delivered, pending, and over the whole range gained,
+        lost, moved, reterm, leaderless (include/raft_engine.h raft_watch_info)."""
+        g0, n = self._watch_args(g0, n, max_events, "poll_leaders")
+        fn = self._lib.raft_engine_poll_leaders
+        if peek:
+            return self._poll(fn, g0, n, 0, 0, "poll_leaders"), np.zeros(0, dtype=abi.EVENT_DTYPE)
+        if max_events is None:
+            max_events = self._poll(fn, g0, n, 0, 0, "poll_leaders")["pending"]
+        out = np.zeros(max(1, int(max_events)), dtype=abi.EVENT_DTYPE)   # never a null buffer: that would be a peek
+        info = self._poll(fn, g0, n, out.ctypes.data, int(max_events), "poll_leaders")
+        return info, out[: info["delivered"]]
+
+    def poll_leaders_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None,
+                         after_stream: int | None = None) -> dict:
+        """poll_leaders into a DEVICE buffer of max_events 24-byte records (8-byte
+        aligned); returns the info once the kernels finished."""
+        g0, n = self._watch_args(g0, n, max_events, "poll_leaders_dev")
+        if max_events is None or (max_events > 0 and not out_ptr):
+            raise ValueError("poll_leaders_dev: a device buffer and its max_events are required")
+        if out_ptr % 8:
+            raise ValueError("poll_leaders_dev: the record buffer must be 8-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._poll(self._lib.raft_engine_poll_leaders_dev, g0, n, out_ptr, max_events, "poll_leaders_dev")
+
+    def read_watch(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """What the watch last reported for groups [g0, g0 + n): [n, 2] int32
+        (leader, term), (-1, 0) before the first report."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(int(n), 0), 2), dtype=np.int32)           # a bad range is the library's to refuse
+        self._check(self._lib.raft_engine_read_watch(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "read_watch")
+        return out
+
+    def write_watch(self, seen: np.ndarray, g0: int = 0):
+        """Store the watch's pairs of groups [g0, g0 + len(seen)) (resuming a
+        consumer): an integer [n, 2] array of (leader in -1..R-1, term >= 0),
+        a leader of -1 with term 0 only."""
+        a = np.asarray(seen)
+        if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
+            raise ValueError(f"write_watch: seen {a.shape} {a.dtype} must be an integer array of shape (n, 2)")
+        if a.size and (a[:, 0].min() < -1 or a[:, 0].max() >= self.R or a[:, 1].min() < 0
+                       or a[:, 1].max() > 0x7FFFFFFF or (a[a[:, 0] < 0, 1] != 0).any()):
+            raise ValueError(f"write_watch: every pair must be (-1, 0) or (leader in 0..{self.R - 1}, term >= 0)")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        self._check(self._lib.raft_engine_write_watch(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "write_watch")
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

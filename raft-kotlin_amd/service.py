@@ -28,6 +28,9 @@ argument meaning and error behaviour:
 * ``RaftService.assert_leadership``: a new leader's no-op entry (Raft thesis
   §3.6.2), so that an idle group commits what earlier terms left and serves
   linearizable reads; ``entries()`` shows it as ``RaftService.NOOP_COMMAND``
+* ``RaftService.watch_leaders`` / ``newest_leader``: a leader directory kept
+  up to date from the engine's leader watch -- only the groups whose leader or
+  term changed since the last call cross the bus (etcd's SoftState in a Ready)
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -410,6 +413,34 @@ class RaftService:
         """The group's leader node (the lowest id when there are several), or
         None: one 16-byte read, not RaftNode.state on every replica."""
         r = int(self.engine.leaders(group, 1)["leader"][0])
+        return None if r < 0 else RaftNode(self, group, r)
+
+    # -- the leader watch: a routing table kept from deltas (etcd's SoftState, TiKV's role observer) ---
+    def watch_leaders(self, max_events: Optional[int] = None) -> np.ndarray:
+        """Bring the cached leader directory up to date: one RaftEngine.poll_leaders
+        of every group, its events (abi.EVENT_DTYPE, ascending group order)
+        applied to ``leader_of`` / ``term_of`` -- two numpy arrays, one entry
+        per group, (-1, 0) where the group has no leader -- and returned.  Only
+        the groups whose newest leader or term changed since the last call
+        cross the bus.  With max_events the rest stays pending for the next
+        call; ``last_watch`` keeps the poll's info.  The directory mirrors the
+        engine's watch: this service must be its only consumer, and after
+        RaftEngine.reset or write_watch it starts over (``del leader_of``)."""
+        if not hasattr(self, "leader_of"):
+            self.leader_of = np.full(self.engine.G, -1, dtype=np.int32)
+            self.term_of = np.zeros(self.engine.G, dtype=np.int32)
+        self.last_watch, ev = self.engine.poll_leaders(max_events=max_events)
+        self.leader_of[ev["group"]] = ev["leader"]
+        self.term_of[ev["group"]] = ev["term"]
+        return ev
+
+    def newest_leader(self, group: int) -> Optional[RaftNode]:
+        """The group's newest leader node as of the last watch_leaders (the
+        LEADER of the highest term, never a deposed one that still holds the
+        role), or None: a lookup in the cached directory, no device call."""
+        if not 0 <= group < self.engine.G:
+            raise IndexError(group)
+        r = int(self.leader_of[group]) if hasattr(self, "leader_of") else -1
         return None if r < 0 else RaftNode(self, group, r)
 
     def submit(self, groups, commands: List[str]) -> np.ndarray:
