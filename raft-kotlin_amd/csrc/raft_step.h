@@ -401,8 +401,6 @@ __device__ __forceinline__ void log_add(const LogView& lv, Rep n, int32_t i, Ent
     overflow = TB ? act & lm(i >= lv.cap) : act & app & lm(phys >= lv.cap);
     wrote = act & ~overflow;
     miss = CHK ? (TB ? wrote : wrote & ~app) & lv.miss(i, phys) : 0ull;
-    // the one slot the new tail cache needs from HBM
-    const uint64_t ld = wrote & (ghost | (AT_END ? 0ull : ~app & ige1 & lm(i != last - 1)));
     const bool ap = ib(app);
     // the new tail cache without HBM (every value but the loaded slot's)
     int32_t t1 = e.term;
@@ -410,8 +408,12 @@ __device__ __forceinline__ void log_add(const LogView& lv, Rep n, int32_t i, Ent
     int32_t t2 = ap ? n.t1 : (i == 0 ? 0 : n.t2);
     // rare: the slot is read only if some lane of the wave needs it, and its
     // value is consumed inside the branch, so the wave waits (vmcnt, which
-    // also counts its earlier log stores) only when a load was issued
-    if (ld) {
+    // also counts its earlier log stores) only when a load was issued.  One
+    // conservative wave-uniform test guards it (a write that is no plain
+    // append at the physical end); the exact lanes are made inside.
+    if (RARE(wrote & (TB ? ~app : lm(phys != last) | ~app))) {
+        // the one slot the new tail cache needs from HBM
+        const uint64_t ld = wrote & (ghost | (AT_END ? 0ull : ~app & ige1 & lm(i != last - 1)));
         if (ib(ld)) {
             const uint2 g = *lv.template at<RNG>(AT_END ? last : (ap ? last : i - 1));
             t1 = ap ? (int32_t)g.x : t1;                    // ghost: log[last] is the new last entry
@@ -680,7 +682,6 @@ struct Ctx {
 // sides, or the drop uniform j = 2*dd + b (word dd, half b); self never lost.
 // d is this lane's replica (c.iso_me, c.part_me are its isolation and
 // partition-side masks).
-// mself: the lanes where d == s (the caller's lm(r == s)).
 // lost_net: the network part (isolation, partition) of sender s's messages,
 // made once per round for both directions.  (Skipping its compares in waves
 // with no isolation or partition measured slower: the branches cost more
@@ -693,10 +694,21 @@ __device__ __forceinline__ uint64_t lost_net(const Ctx<R>& c, int s) {
         net |= c.part_me ^ lm(__builtin_amdgcn_ubfe(c.part, (uint32_t)s, 1u));    // s, d on two sides
     return net;
 }
+// lost: the lanes of a round's senders-to-others `far` (the caller's mask, self
+// excluded once) whose request is lost (lreq) and whose request or response is
+// lost (gone = lreq | lresp: a response exists only where the request arrived,
+// and the network part loses both directions alike, so the response's loss
+// adds only its own drop uniform).
 template <int NET>
-__device__ __forceinline__ uint64_t lost(const DevParams& p, uint64_t net, uint64_t mself, uint32_t dw, int b) {
-    if constexpr (!(NET & NET_DROP)) return ~mself & net;
-    else return ~mself & (net | lm(((dw >> (16 * b)) & 0xFFFFu) < p.drop_thr16));
+__device__ __forceinline__ void lost(const DevParams& p, uint64_t far, uint64_t net, uint32_t dw, uint64_t& lreq,
+                                     uint64_t& gone) {
+    if constexpr (!(NET & NET_DROP)) {
+        lreq = gone = far & net;
+    } else {
+        const uint64_t lq = net | lm((dw & 0xFFFFu) < p.drop_thr16);
+        lreq = far & lq;
+        gone = far & (lq | lm((dw >> 16) < p.drop_thr16));
+    }
 }
 
 // 16-bit drop uniforms of sender s for this lane as destination d (S-9):
@@ -847,22 +859,28 @@ struct Stepper {
         uint32_t dw;
         if constexpr (STAGED) dw = drops_off<NET>(p) ? 0u : job_drop_word(c, s, s);   // stage_sender_chunks
         else dw = drop_word<R, L::TICK_JOB, NET>(p, c, RAFT_RNG_APPEND_DROP, run, s, c.dwt, c.s_tick);
-        const uint64_t cancel = mtk & ~run & mme;                         // :117 cancel() (S-10)
-        if (RARE(cancel)) n.fl &= ib(cancel) ? ~FL_HB : ~0u;
         cnt.add(run & mme, RAFT_C_SESSIONS_TICKED);
-        const uint64_t swap = run & lm(n.s0 != s);                        // swap the session in (rare)
-        if (RARE(swap)) {
-            BSTAT(c, BS_A_SWAP);
-            if (ib(swap)) {
-                if (n.s0 >= 0) spill_store(p, c, n, n.s0);
-                spill_load(p, c, n, s);
-                // wait for the loads here: consumed after the branch, they
-                // would put a vmcnt wait (which also counts this tick's log
-                // store) on the common path
-                asm volatile("" :: "v"(n.nx), "v"(n.mc));
+        // the two rare session events behind one wave-uniform test: the owner
+        // is no leader any more (run is within mtk and whole groups, so the
+        // groups of mtk ^ run are the ones that cancel), or the session is
+        // not the primary one and is swapped in
+        const uint64_t stale = mtk ^ run;
+        const uint64_t swap = run & lm(n.s0 != s);
+        if (RARE(stale | swap)) {
+            n.fl &= ib(stale & mme) ? ~FL_HB : ~0u;                       // :117 cancel() (S-10)
+            if (swap) {
+                BSTAT(c, BS_A_SWAP);
+                if (ib(swap)) {
+                    if (n.s0 >= 0) spill_store(p, c, n, n.s0);
+                    spill_load(p, c, n, s);
+                    n.s0 = s;
+                    // wait for the loads here: consumed after the branch, they
+                    // would put a vmcnt wait (which also counts this tick's log
+                    // store) on the common path
+                    asm volatile("" :: "v"(n.nx), "v"(n.mc));
+                }
             }
         }
-        n.s0 = ib(swap) ? s : n.s0;
         // build this destination's request (RaftServer.kt:122-132).  With
         // prev = i - 2: Log.get(prev) throws for prev > lastIndex - 1 (:128,
         // Q11) and log[i-1] for i < 1 (:131), so the request goes out iff
@@ -913,9 +931,9 @@ struct Stepper {
         // in an earlier basic block (before the handler's log store) would be
         // re-materialised through a VGPR
         const uint64_t net = lost_net<R, NET>(c, s);
-        const uint64_t lreq = ok & lost<NET>(p, net, mme, dw, 0);         // :170-172
+        uint64_t lreq, gone;                                              // :170-172
+        lost<NET>(p, ok & ~mme, net, dw, lreq, gone);
         const uint64_t act = ok & ~lreq;
-        const uint64_t lresp = act & lost<NET>(p, net, mme, dw, 1);
         int32_t rterm;
         uint64_t succ, stored;
         // no lane of act throws: ok implies prev >= -1
@@ -969,14 +987,14 @@ struct Stepper {
                 n.commit = ib(succ & lm(Lcommit > n.commit)) ? cc : n.commit;
             }
         }
-        const uint64_t delivered = act & ~lresp;
-        cnt.add(lreq | lresp, RAFT_C_MSG_DROPPED);
+        const uint64_t delivered = ok & ~gone;
+        cnt.add(gone, RAFT_C_MSG_DROPPED);
 
         // responses in destination order (S-4).  :146-154 (Q7): a response
         // with a term above the running term adopts it and skips the rest of
         // that response; the running term is the prefix max.
         int32_t T = Lterm;
-        uint64_t sdb = 0;                                                 // responses that stepped down
+        uint64_t nd = delivered;                                          // responses that did not step down
         const uint64_t hib = delivered & lm(rterm > Lterm);
         bool stepdown = false;
         if (RARE(hib)) {                                                  // wave-uniform, rare
@@ -988,13 +1006,13 @@ struct Stepper {
                 const int32_t rq = bcast(rterm, c.src(q));
                 const uint64_t up = lm((dl >> q) & 1u) & lm(rq > T);
                 T = ib(up) ? rq : T;
-                sdb |= up & L::lanes_of(q);                               // response q stepped down
+                nd &= ~(up & L::lanes_of(q));                             // response q stepped down
             }
         }
         const int32_t mc_old = n.mc;
-        const uint64_t nd = delivered & ~sdb;
-        const uint64_t chk = nd & succ & has;                             // :156-162 (Q9)
-        const uint64_t hbk = nd & succ & ~has;                            // :163-164
+        const uint64_t ack = nd & succ;
+        const uint64_t chk = ack & has;                                   // :156-162 (Q9)
+        const uint64_t hbk = ack & ~has;                                  // :163-164
         const uint64_t nak = nd & ~succ;                                  // :166-167
         if constexpr (TB) {
             // TB: nextIndex += the entries acked, matchIndex = the last one's index
@@ -1008,7 +1026,10 @@ struct Stepper {
             }
         } else {
             n.nx = dec_if(inc_if(n.nx, chk), nak);                       // chk and nak are disjoint
-            n.mc = ib(hbk) ? prev + 1 : inc_if(mc_old, chk);
+            // prev + 1 on a heartbeat's ack, matchIndex + 1 on an entry's:
+            // one select and one add with carry (a select between the two
+            // sums compiles to an exec-mask branch around inc_if)
+            n.mc = inc_if(ib(hbk) ? prev : mc_old, ack);
             cnt.add(chk, RAFT_C_ENTRIES_ACKED);
         }
         // commit rule, after each acknowledged entry in destination order:
@@ -1025,36 +1046,40 @@ struct Stepper {
             // after the tick, the rest as before it.  If fewer than a majority
             // of rows ends above Lcommit + 1, a second increment is impossible.
             // Otherwise (a row went down, or a majority ends above Lcommit + 1:
-            // a lagging commitIndex, Q9) the replay below runs.
-            const uint64_t hi2 = run & lm(n.mc > C + 1);                 // (the ticking groups' rows)
-            uint64_t slow = run & lm(n.mc < mc_old);
-            if (RARE(hi2)) slow |= lm(__popc(c.gbits(hi2)) >= MAJ);             // wave-uniform, rare
-            if (LIKELY(!slow)) {
-                const uint64_t upto = lm((ck >> c.r) != 0u);              // rows at or before q*
-                const int32_t cur = ib(upto) ? n.mc : mc_old;
-                const uint64_t inc = lm(__popc(c.gbits(lm(cur > C))) >= MAJ) & lm(ck != 0u);   // :161-162
-                C = inc_if(C, inc);
-                cnt.add(inc & L::lanes_of(0), RAFT_C_COMMITS);            // one lane per group
-            } else {
-                BSTAT(c, BS_A_SLOW);
-                // the replay in destination order.  Bit q of the group's acks,
-                // pre-shifted so that one v_bcnt adds it (as 16 << q) to the
-                // popcount: pc >= (16 << q) + MAJ tests "response q acked and
-                // count >= majority" in one compare
-                const uint32_t ck16 = ck << 4;
-                uint64_t commits = 0;                                     // one lane per increment
+            // a lagging commitIndex, Q9) the replay below runs instead.  The
+            // closed form is on the common path with no branch around it; one
+            // wave-uniform test covers both exceptions, which start over.
+            const uint64_t upto = lm((ck >> c.r) != 0u);                  // rows at or before q*
+            const int32_t cur = ib(upto) ? n.mc : mc_old;
+            const uint64_t inc = lm(__popc(c.gbits(lm(cur > C))) >= MAJ) & lm(ck != 0u);   // :161-162
+            C = inc_if(C, inc);
+            uint64_t commits = inc & L::lanes_of(0);                      // one lane per group
+            const uint64_t hi2 = run & lm(n.mc > Lcommit + 1);           // (the ticking groups' rows)
+            const uint64_t down = run & lm(n.mc < mc_old);
+            if (RARE(hi2 | down)) {                                       // wave-uniform, rare
+                const uint64_t slow = down | lm(__popc(c.gbits(hi2)) >= MAJ);
+                if (slow) {
+                    BSTAT(c, BS_A_SLOW);
+                    // the replay in destination order.  Bit q of the group's acks,
+                    // pre-shifted so that one v_bcnt adds it (as 16 << q) to the
+                    // popcount: pc >= (16 << q) + MAJ tests "response q acked and
+                    // count >= majority" in one compare
+                    const uint32_t ck16 = ck << 4;
+                    C = Lcommit;
+                    commits = 0;                                          // one lane per increment
 #pragma unroll
-                for (int q = 0; q < R; ++q) {
-                    if (!(chk & L::lanes_of(q))) continue;                // wave-uniform
-                    const int32_t cur = ib(L::lanes_upto(q)) ? n.mc : mc_old;   // rows after / before response q
-                    const uint32_t gt = c.gbits(lm(cur > C));             // :161
-                    const uint32_t pc = __popc(gt) + (ck16 & (16u << q));
-                    const uint64_t inc = lm(pc >= (16u << q) + MAJ);      // :162 (whole groups)
-                    C = inc_if(C, inc);
-                    commits |= inc & L::lanes_of(q);                      // disjoint lanes per q
+                    for (int q = 0; q < R; ++q) {
+                        if (!(chk & L::lanes_of(q))) continue;            // wave-uniform
+                        const int32_t cur = ib(L::lanes_upto(q)) ? n.mc : mc_old;   // rows after / before response q
+                        const uint32_t gt = c.gbits(lm(cur > C));         // :161
+                        const uint32_t pc = __popc(gt) + (ck16 & (16u << q));
+                        const uint64_t inc = lm(pc >= (16u << q) + MAJ);  // :162 (whole groups)
+                        C = inc_if(C, inc);
+                        commits |= inc & L::lanes_of(q);                  // disjoint lanes per q
+                    }
                 }
-                cnt.add(commits, RAFT_C_COMMITS);
             }
+            cnt.add(commits, RAFT_C_COMMITS);
         }
         if constexpr (TB) {
             // textbook commit rule: N = the majority-th largest matchIndex of the
@@ -1133,14 +1158,14 @@ struct Stepper {
         const uint64_t mine = mvr & lm((ms >> r) & 1u);
         const uint64_t mme = lm(r == s);
         const uint64_t net = lost_net<R, NET>(c, s);
-        const uint64_t lreq = mine & lost<NET>(p, net, mme, dw, 0); // retry{} swallows, Commons.kt:41
+        uint64_t lreq, gone;                                        // retry{} swallows, Commons.kt:41
+        lost<NET>(p, mine & ~mme, net, dw, lreq, gone);
         const uint64_t act = mine & ~lreq;
         int32_t rterm;
         uint64_t granted;
         vote_handler<TB, RING>(n.rep(), act, r + 1, rt, s + 1, rli, rlt, gapw, hasl, fs, cnt, rterm, granted);
-        const uint64_t lresp = act & lost<NET>(p, net, mme, dw, 1);
-        const uint64_t delivered = act & ~lresp;
-        cnt.add(lreq | lresp, RAFT_C_MSG_DROPPED);
+        const uint64_t delivered = mine & ~gone;
+        cnt.add(gone, RAFT_C_MSG_DROPPED);
         const uint64_t him = delivered & lm(rterm > st);
         uint32_t hi = 0;
         if (RARE(him)) hi = c.gbits(him);                                 // wave-uniform, rare
