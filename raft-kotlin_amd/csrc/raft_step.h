@@ -530,7 +530,7 @@ __device__ __forceinline__ uint64_t append_handler(Rep n, uint64_t act, int32_t 
     }
     log_add<TB, CHK, CHK>(lv, n, prev + 1, e, success & has & ~same, at_last, p0, wrote, ovf, wmiss);   // :278 (Q2, Q10)
     cnt.add(wrote, RAFT_C_ENTRY_WRITES);
-    cnt.add(ovf, RAFT_C_LOG_OVERFLOW);
+    if (RARE(ovf)) cnt.add(ovf, RAFT_C_LOG_OVERFLOW);                           // behind the test its mask's last AND made
     if constexpr (CHK) cnt.add(wmiss, RAFT_C_LOG_WINDOW_MISS);                 // the write
     stored = wrote | same;                                                      // TB: the entry is in place
     if constexpr (TB) {
@@ -548,7 +548,7 @@ __device__ __forceinline__ void append_command(Rep n, uint64_t act, const LogVie
     uint64_t wrote, ovf, wmiss;
     log_add<TB, CHK && TB, CHK, true>(lv, n, n.last, Entry{n.term, cmd}, act, ~0ull, 0ull, wrote, ovf, wmiss);   // the reference
     cnt.add(act, RAFT_C_COMMANDS);                                              // appends at physLen: no miss;
-    cnt.add(ovf, RAFT_C_LOG_OVERFLOW);                                          // TB writes slot lastIndex
+    if (RARE(ovf)) cnt.add(ovf, RAFT_C_LOG_OVERFLOW);                           // TB writes slot lastIndex
     if constexpr (CHK && TB) cnt.add(wmiss, RAFT_C_LOG_WINDOW_MISS);
 }
 
@@ -1229,8 +1229,12 @@ struct Stepper {
         uint32_t send;
         int32_t qt, qli, qlt;
         uint64_t sstart;
+        // made by T's busy branch, 0 in a quiet wave: the lanes in a vote
+        // round after T, which is D's `inr` (neither H nor V changes
+        // FL_ELECTING or FL_BACKOFF)
+        uint64_t inr;
         auto phase_t = [&](Ctx<R>& c, Node& n, Counters& cnt, uint32_t& send, int32_t& qt, int32_t& qli, int32_t& qlt,
-                           uint64_t& sstart) {
+                           uint64_t& sstart, uint64_t& inr) {
             // ---------------- T: timers and election clocks ----------------
             // a wave where no timer fires and no replica is electing only counts
             // its armed timers down (most waves in steady state)
@@ -1244,6 +1248,7 @@ struct Stepper {
             // made the register allocator copy a dozen values on it)
             n.elec = ib(t_armed) ? t_el : n.elec;
             send = 0u; sstart = 0; qt = qli = qlt = 0;
+            inr = 0;
             if (t_fire | electing) {
                 BSTAT(c, BS_T_BUSY);
                 uint32_t f = n.fl;
@@ -1283,13 +1288,18 @@ struct Stepper {
                 cnt.add((sr | resend) & lm(n.last != 0), RAFT_C_VOTE_LOG_READS);
                 if constexpr (RING) cnt.add((sr | resend) & lm(n.last != 0) & lm(n.phys - n.last >= p.W), RAFT_C_LOG_WINDOW_MISS);
                 cnt.add(sr, RAFT_C_ROUNDS);
+                // in a vote round after T: a round that started or restarted
+                // (fr clears FL_BACKOFF), or one that goes on (in_round lanes
+                // keep f; endel and restart are within in_bo, start_fire outside
+                // electing).  The other electing lanes are in backoff or ended.
+                inr = sr | in_round;
+                if (RARE(sstart)) start_sessions(p, c, n, sstart, cnt);         // an election ended as LEADER
             }
-            start_sessions(p, c, n, sstart, cnt);
         };
-        RAFT_TWICE(PH_T, ({ uint32_t s_; int32_t a_, b_, d_; uint64_t e_;
-                            phase_t(c2, n2, k2, s_, a_, b_, d_, e_);
-                            asm volatile("" ::"v"(s_), "v"(a_), "v"(b_), "v"(d_), "s"(e_)); }));
-        phase_t(c, n, cnt, send, qt, qli, qlt, sstart);
+        RAFT_TWICE(PH_T, ({ uint32_t s_; int32_t a_, b_, d_; uint64_t e_, i_;
+                            phase_t(c2, n2, k2, s_, a_, b_, d_, e_, i_);
+                            asm volatile("" ::"v"(s_), "v"(a_), "v"(b_), "v"(d_), "s"(e_), "s"(i_)); }));
+        phase_t(c, n, cnt, send, qt, qli, qlt, sstart, inr);
         c.clk.mark(PH_T);
 
         // ---------------- the step's Philox pass (S-9) ----------------
@@ -1421,15 +1431,12 @@ struct Stepper {
         c.clk.mark(PH_V);
         // ---------------- D: latch closes -> decision (RaftServer.kt:214-222) ----------------
         // only waves where some round closes this step do any of it
+        // (inr: the lanes in a vote round, phase T's output; 0 in a quiet wave)
         uint64_t dstart = 0, need_bo = 0;
-        {
+        if (inr) {                                                          // wave-uniform
             const uint32_t f = n.fl;
-            const uint64_t inr = lm(f & FL_ELECTING) & ~lm(f & FL_BACKOFF);     // in a vote round
-            uint64_t dec = 0;
-            if (inr) {                                                      // wave-uniform
-                const int latch = (f >> LATCH_SH) & 0xF;
-                dec = inr & (lm(latch >= MAJ) | lm(n.phase >= p.round_to));
-            }
+            const int latch = (f >> LATCH_SH) & 0xF;
+            const uint64_t dec = inr & (lm(latch >= MAJ) | lm(n.phase >= p.round_to));
             if (dec) {                                                      // wave-uniform
                 BSTAT(c, BS_D_DEC);
                 const int votes = (f >> VOTES_SH) & 0xF;
@@ -1454,13 +1461,15 @@ struct Stepper {
             const KernArgs kp = kernargs();
             if (ib(need_bo)) n.phase = scale_range(w, kp->bmin, kp->bmax);
         }
-        if (dstart) BSTAT(c, BS_D_START);
-        start_sessions(p, c, n, dstart, cnt);
+        uint32_t todo = hb;
+        if (RARE(dstart)) {                                                 // D started a session (FL_HB set)
+            BSTAT(c, BS_D_START);
+            start_sessions(p, c, n, dstart, cnt);
+            todo = c.gbits(__ballot((n.fl & FL_HB) != 0));
+        }
         c.clk.mark(PH_D);
 
         // ---------------- A: leader ticks, senders ascending (S-3, S-4) ----------------
-        uint32_t todo = hb;
-        if (RARE(dstart)) todo = c.gbits(__ballot((n.fl & FL_HB) != 0));   // D started a session
         // the first round peeled: the common case runs no loop (a loop makes
         // the compiler carry the counters in VGPRs and copy the node per round).
         // mt: the lanes of groups with a session left to tick (each round's
