@@ -64,6 +64,7 @@ extern "C" {
 #define RAFT_ENODEV       -5   /* no HIP device / kernel image unavailable   */
 #define RAFT_EWINDOW      -6   /* a handler batch touched a log slot below the
                                 * retained window (results invalid, like overflow) */
+#define RAFT_EFULL        -7   /* the outbox has no room for the batch: nothing was enqueued */
 
 /* ---- node roles: enum class State (RaftServer.kt:24-26) --------------- */
 #define RAFT_FOLLOWER  0
@@ -1213,6 +1214,141 @@ int raft_engine_poll_leaders_dev(raft_engine* e, int64_t g0, int64_t n, raft_lea
  * -1 with term 0 only; anything else is RAFT_EINVAL and nothing is stored. */
 int raft_engine_read_watch (raft_engine* e, int64_t g0, int64_t n, int32_t* out);
 int raft_engine_write_watch(raft_engine* e, int64_t g0, int64_t n, const int32_t* in);
+
+/* ---- the proposal outbox: retry lost proposals on the device, commit once -----
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * raft_propose_batch hands out a ticket and raft_engine_resolve_tickets says
+ * what became of it; what a client does with a proposal that did not commit
+ * (Raft thesis §6.3: "the client retries") is left to the caller.  The outbox
+ * is that piece: a queue in HBM, opt-in per engine, that holds proposals until
+ * they are committed, re-proposes exactly the ones that are provably gone and
+ * hands completions out as a stream.  The step kernel, the canonical state and
+ * the digest do not know about it; an engine that never configures one behaves
+ * as before, byte for byte.  The reference has no counterpart (its /cmd route
+ * forgets the command at once).
+ *
+ * Why "retry whatever resolved LOST" is wrong.  RAFT_TICKET_LOST says that the
+ * ticket's own replica no longer holds the entry, nothing about the others.
+ * Leader A appends (i, T, c) and replicates it to B; A's slot i is overwritten
+ * by a short-lived leader of term T+1 whose entry reached A only; the ticket
+ * resolves LOST with holders = 1.  B can still win term T+2 on the votes of
+ * replicas that never saw the T+1 entry and commit (i, T, c): a client that
+ * re-proposed c has committed it twice.  Only holders == 0 is final: no replica
+ * has the entry, the engine has no message in flight between two steps, so
+ * nothing can bring it back.
+ *
+ * A record (raft_outbox_entry, 48 bytes, the export form) is a proposal (group,
+ * cmd) under the caller's tag, the step index at its submit (born), its current
+ * raft_ticket (replica, index, term, status; (-1, -1, 0, RAFT_OUTBOX_NEW)
+ * before the first proposal) and the number of times it was proposed (tries).
+ *
+ * raft_engine_outbox_configure(capacity, expire_steps): capacity >= 1 records,
+ *   expire_steps >= 0 (0: never); anything else is RAFT_EINVAL.  Allocates the
+ *   queue (2 x capacity x 48 bytes: a pump writes the survivors into the other
+ *   half), which counts in raft_engine_device_bytes from then on and which
+ *   raft_engine_trim_staging keeps (it frees the outbox's scratch).  The queue
+ *   shares its allocation with the leader watch's `seen` pairs, which are
+ *   allocated with it (8 bytes per group) if no call has needed them yet and
+ *   keep their contents otherwise.  An empty outbox may be configured again; a
+ *   non-empty one is RAFT_EINVAL.  raft_engine_reset empties the outbox and
+ *   keeps its configuration.
+ * raft_outbox_submit(group, cmd, tag, n): appends n records at the tail in
+ *   batch order with status NEW, tries 0, born = raft_engine_step_index now.
+ *   It proposes nothing.  RAFT_EINVAL: not configured, null array with n > 0,
+ *   n < 0; RAFT_EFULL: n exceeds the free room; RAFT_ERANGE: a group outside
+ *   the engine.  In each case nothing is enqueued.  n == 0 is RAFT_OK.
+ * raft_engine_outbox_pump(done, max_done, n_done, info): two phases, on the
+ *   state the call finds.
+ *   Phase 1 gives every record a verdict from raft_engine_resolve_tickets'
+ *   record of its ticket (a ticket of status NEW, NO_LEADER or LOG_FULL stored
+ *   nothing: RAFT_TICKET_NONE); phase 2 changes no verdict.  With age = the
+ *   step index now - born, the first match of:
+ *     1. COMMITTED                               -> done, RAFT_OUTBOX_COMMITTED
+ *     2. expire_steps > 0 and age >= expire_steps -> done, RAFT_OUTBOX_EXPIRED:
+ *        the outcome is unknown, as after any client timeout (the entry may
+ *        still commit later)
+ *     3. UNKNOWN                                 -> kept (info.unknown)
+ *     4. PENDING                                 -> kept (info.pending)
+ *     5. LOST with holders >= 1                  -> kept (info.orphaned)
+ *     6. LOST with holders == 0, or NONE         -> retried (info.retried)
+ *   Phase 2: the first max_done done records in queue order are written to
+ *   done[] in that order and leave the queue; the done records past the cut
+ *   stay unchanged (info.deferred).  The retried records are proposed, in queue
+ *   order, with exactly the effect of one raft_propose_batch over their
+ *   (group, cmd): the same leader rule, the k-th accepted message to a group
+ *   gets lastIndex + k, the same RAFT_EWINDOW rule.  Each one's ticket is
+ *   replaced by the new one and its tries grow by 1 (a NO_LEADER or LOG_FULL
+ *   ticket keeps the record for the next pump).  The queue becomes the surviving
+ *   records in their original order.
+ *   *n_done = records written (<= max_done).  RAFT_EINVAL: not configured, null
+ *   n_done or info, max_done < 0, done == NULL with max_done > 0, a _dev buffer
+ *   that is not 16-byte aligned.  Otherwise RAFT_EWINDOW when info.unknown > 0
+ *   or a retried add was below its replica's window, after doing everything;
+ *   otherwise RAFT_OK.
+ *   info: queued = the queue's length at the call = committed + expired +
+ *   deferred + pending + orphaned + unknown + retried; committed / expired
+ *   count the records written to done[]; accepted + ghosted + no_leader +
+ *   log_full = retried, by the status of the new tickets; left = the queue's
+ *   length afterwards = queued - committed - expired.  age_hist counts the
+ *   COMMITTED records this call wrote, in bucket min(31, floor(log2(age + 1))).
+ * raft_engine_outbox_read(out, room, n): the queue in order, *n records.  out ==
+ *   NULL with room 0 is a peek: RAFT_OK with *n = the queue's length; otherwise
+ *   a room below the length is RAFT_EINVAL, with *n = the length and nothing
+ *   copied.  raft_engine_outbox_write(in, n): replaces the queue.
+ *   Refused before anything is stored: n above the capacity (RAFT_EFULL), a
+ *   group outside the engine (RAFT_ERANGE), a status that is none of
+ *   RAFT_OUTBOX_NEW / RAFT_PROPOSE_*, a ticket that stored an entry (ACCEPTED,
+ *   GHOSTED, CURRENT) with a replica outside -1..R-1 or an index outside
+ *   0..log_cap-1, tries < 0, a nonzero pad (RAFT_EINVAL).
+ *
+ * Promised: in RAFT_MODE_TEXTBOOK without RAFT_RESTART_AMNESIA no record's
+ * command is ever committed under two different (index, term) -- provided the
+ * caller submits each command once and proposes it through the outbox only.
+ * Not promised: anything in reference mode (quirks Q1, Q4, Q9 lose and
+ * duplicate entries on their own; the calls are defined and deterministic all
+ * the same); progress in an idle group, which needs an entry of the current
+ * term to commit older ones (raft_engine_append_noops).
+ *
+ * Ordering is raft_engine_drain_committed's: the calls run on the engine
+ * stream, see every step enqueued before them, and later step launches wait
+ * for them.  The _dev variants take DEVICE pointers for the arrays (n_done and
+ * info stay host pointers) and return after their kernels finished. */
+#define RAFT_OUTBOX_NEW       (-1)  /* raft_outbox_entry.status before the first proposal */
+#define RAFT_OUTBOX_COMMITTED  1    /* raft_outbox_done.status */
+#define RAFT_OUTBOX_EXPIRED    2
+typedef struct raft_outbox_entry {   /* 48 bytes */
+    int64_t  tag;        /* the caller's */
+    int64_t  born;       /* raft_engine_step_index at the submit */
+    int32_t  group;      /* engine-local */
+    uint32_t cmd;
+    int32_t  replica, index, term, status;   /* the record's raft_ticket; status RAFT_OUTBOX_NEW or RAFT_PROPOSE_* */
+    int32_t  tries;      /* proposals made for it so far */
+    int32_t  pad;        /* 0 */
+} raft_outbox_entry;
+typedef struct raft_outbox_done {    /* 32 bytes */
+    int64_t tag;
+    int32_t group;
+    int32_t status;      /* RAFT_OUTBOX_COMMITTED / RAFT_OUTBOX_EXPIRED */
+    int32_t index, term; /* of the record's last ticket: where it committed (COMMITTED) */
+    int32_t tries;
+    int32_t age;         /* the step index at this pump - born, clipped to int32 */
+} raft_outbox_done;
+typedef struct raft_outbox_info {    /* 360 bytes, all int64 */
+    int64_t queued, committed, expired, deferred, pending, orphaned, unknown, retried;
+    int64_t accepted, ghosted, no_leader, log_full, left;
+    int64_t age_hist[32];
+} raft_outbox_info;
+int raft_engine_outbox_configure(raft_engine* e, int64_t capacity, int32_t expire_steps);
+int raft_outbox_submit    (raft_engine* e, const int64_t* group, const uint32_t* cmd, const int64_t* tag, int64_t n);
+int raft_outbox_submit_dev(raft_engine* e, const int64_t* group_dev, const uint32_t* cmd_dev, const int64_t* tag_dev,
+                           int64_t n);
+int raft_engine_outbox_pump    (raft_engine* e, raft_outbox_done* done_host, int64_t max_done, int64_t* n_done,
+                                raft_outbox_info* info);
+int raft_engine_outbox_pump_dev(raft_engine* e, raft_outbox_done* done_dev, int64_t max_done, int64_t* n_done,
+                                raft_outbox_info* info);
+int raft_engine_outbox_read (raft_engine* e, raft_outbox_entry* out, int64_t room, int64_t* n);
+int raft_engine_outbox_write(raft_engine* e, const raft_outbox_entry* in, int64_t n);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

@@ -24,6 +24,7 @@ RAFT_EDEVICE = -3
 RAFT_ERANGE = -4
 RAFT_ENODEV = -5
 RAFT_EWINDOW = -6
+RAFT_EFULL = -7
 COMM_ID_BYTES = 128          # include/raft_engine.h RAFT_COMM_ID_BYTES
 
 # enum class State (RaftServer.kt:24-26)
@@ -333,6 +334,25 @@ WATCH_INFO_FIELDS = ("delivered", "pending", "gained", "lost", "moved", "reterm"
 WATCH_UNSEEN = (-1, 0)
 
 
+class raft_outbox_info(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("queued", "committed", "expired", "deferred", "pending", "orphaned", "unknown",
+                                         "retried", "accepted", "ghosted", "no_leader", "log_full", "left")] + [
+        ("age_hist", C.c_int64 * 32)]
+
+
+# the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*): raft_outbox_entry (48 bytes) and raft_outbox_done
+# (32 bytes) as numpy records without padding, the scalar fields of raft_outbox_info, the status words
+OUTBOX_ENTRY_DTYPE = np.dtype([("tag", np.int64), ("born", np.int64), ("group", np.int32), ("cmd", np.uint32),
+                               ("replica", np.int32), ("index", np.int32), ("term", np.int32), ("status", np.int32),
+                               ("tries", np.int32), ("pad", np.int32)])
+OUTBOX_DONE_DTYPE = np.dtype([("tag", np.int64), ("group", np.int32), ("status", np.int32), ("index", np.int32),
+                              ("term", np.int32), ("tries", np.int32), ("age", np.int32)])
+OUTBOX_INFO_FIELDS = ("queued", "committed", "expired", "deferred", "pending", "orphaned", "unknown", "retried",
+                      "accepted", "ghosted", "no_leader", "log_full", "left")
+OUTBOX_NEW, OUTBOX_COMMITTED, OUTBOX_EXPIRED = -1, 1, 2
+OUTBOX_DONE_NAMES = {1: "COMMITTED", 2: "EXPIRED"}
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -509,6 +529,13 @@ def load_library(path: str | None = None):
         "raft_engine_poll_leaders_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_watch_info)]),
         "raft_engine_read_watch": (C.c_int, [eng, I64, I64, P(I32)]),
         "raft_engine_write_watch": (C.c_int, [eng, I64, I64, P(I32)]),
+        "raft_engine_outbox_configure": (C.c_int, [eng, I64, I32]),
+        "raft_outbox_submit": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_outbox_submit_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
+        "raft_engine_outbox_pump": (C.c_int, [eng, C.c_void_p, I64, P(I64), P(raft_outbox_info)]),
+        "raft_engine_outbox_pump_dev": (C.c_int, [eng, C.c_void_p, I64, P(I64), P(raft_outbox_info)]),
+        "raft_engine_outbox_read": (C.c_int, [eng, C.c_void_p, I64, P(I64)]),
+        "raft_engine_outbox_write": (C.c_int, [eng, C.c_void_p, I64]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -572,6 +599,8 @@ EXPORTED_SYMBOLS = [
     "raft_engine_resolve_transfers_dev", "raft_engine_evacuate", "raft_engine_evacuate_dev",
     "raft_engine_append_noops", "raft_engine_append_noops_dev", "raft_engine_sm_set_noop",
     "raft_engine_poll_leaders", "raft_engine_poll_leaders_dev", "raft_engine_read_watch", "raft_engine_write_watch",
+    "raft_engine_outbox_configure", "raft_outbox_submit", "raft_outbox_submit_dev", "raft_engine_outbox_pump",
+    "raft_engine_outbox_pump_dev", "raft_engine_outbox_read", "raft_engine_outbox_write",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

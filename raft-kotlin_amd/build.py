@@ -32,10 +32,11 @@ SRCS = [SRC, os.path.join(CSRC, "raft_batch.hip"),                   # the handl
         os.path.join(CSRC, "raft_transfer.hip"),                     # leadership transfer (TimeoutNow, evacuate)
         os.path.join(CSRC, "raft_noop.hip"),                         # leader no-op entries (commit and read liveness)
         os.path.join(CSRC, "raft_watch.hip"),                        # the leader watch (leadership changes as deltas)
+        os.path.join(CSRC, "raft_outbox.hip"),                       # the proposal outbox (retry what is gone, commit once)
         os.path.join(CSRC, "raft_wire.cpp"),                         # the wire codec is host code
         os.path.join(CSRC, "raft_host.cpp"),                         # page-locked batch memory
         os.path.join(CSRC, "raft_comm.cpp")]                         # the RCCL counter all-reduce (dlopen)
-HDRS = [os.path.join(CSRC, h) for h in ("raft_step.h", "philox.h", "raft_engine_impl.h")] + [
+HDRS = [os.path.join(CSRC, h) for h in ("raft_step.h", "philox.h", "raft_engine_impl.h", "raft_ticket.h")] + [
     os.path.join(ROOT, "include", h) for h in ("raft_engine.h", "raft_wire.h")]
 # the step kernel's sources (bench.py's kernel_source_id, the key of its
 # rocprofv3 rows): not raft_batch.hip, which holds no step-kernel code

@@ -26,6 +26,7 @@
 #include <string>
 
 #include "raft_engine_impl.h"
+#include "raft_ticket.h"
 
 using namespace raft;
 
@@ -119,7 +120,6 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(DevParams p, const int64
                                                         const int4* __restrict__ ticket,
                                                         const uint32_t* __restrict__ cmd, int4* __restrict__ out,
                                                         int64_t n, unsigned int* flags) {
-    static_assert(RAFT_MAX_R == 8, "eight lanes per ticket");
     const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const int r = (int)(tid & 7);
     const bool live = (tid >> 3) < n;
@@ -127,52 +127,19 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(DevParams p, const int64
     const int64_t g = group[m];
     const int4 tk = ticket[m];                                          // (replica, index, term, status)
     const uint32_t c = cmd[m];
-    const bool g_ok = g >= 0 && g < p.G;
     const bool stored = tk.w != RAFT_PROPOSE_NO_LEADER && tk.w != RAFT_PROPOSE_LOG_FULL;
-    // the index is checked against log_cap before any slot is read, and masked in a ring (LogView::at)
-    const bool t_ok = tk.x >= -1 && tk.x < p.R && tk.y >= 0 && tk.y < p.cap;
-    uint32_t v = 0;                                                     // holder | committed << 8 | unknown << 16 | own << 24
-    if (g_ok && stored && t_ok && r < p.R) {
-        const int64_t idx = g * p.R + r;
-        const int4 q1 = *quad(p, 1, idx);                               // lastIndex, physLen
-        const int32_t commit = quad(p, 2, idx)->x;
-        const int32_t last = q1.x, phys = q1.y, i = tk.y;
-        if (p.W != FLAT_W && i < phys - p.W) {
-            v = 1u << 16;                                               // below the window: not read
-        } else if (i < last) {
-            const uint2 en = *log_of(p, idx).at<true>(i);
-            if ((int32_t)en.x == tk.z && en.y == c) {
-                const int32_t hi = committed_hi(p, commit, last);
-                v = 1u | (i < hi ? 1u << 8 : 0u) | (r == tk.x ? 1u << 24 : 0u);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v += __shfl_xor(v, d, 64);
+    // (the per-ticket routine, shared with the outbox's verdict pass: raft_ticket.h)
+    const uint32_t v = ticket_sum(ticket_lane(p, g, tk, c, r, stored));
     if (!live || r != 0) return;
-    const int32_t holders = (int32_t)(v & 255u), com = (int32_t)((v >> 8) & 255u), unk = (int32_t)((v >> 16) & 255u);
-    int32_t st;
-    if (!g_ok) {
-        st = RAFT_TICKET_INVALID;
-        atomicOr(&flags[CW_RANGE], 1u);
-    } else if (!stored) {
-        st = RAFT_TICKET_NONE;
-    } else if (!t_ok) {
-        st = RAFT_TICKET_INVALID;
-        atomicOr(&flags[CW_INVAL], 1u);
-    } else if (com >= 1) {
-        st = RAFT_TICKET_COMMITTED;
-    } else if (unk >= 1) {
-        st = RAFT_TICKET_UNKNOWN;
-        atomicOr(&flags[CW_UNKNOWN], 1u);
-    } else {
-        st = (v >> 24) ? RAFT_TICKET_PENDING : RAFT_TICKET_LOST;
-    }
-    out[m] = make_int4(st, holders, com, unk);                          // raft_ticket_state
+    const TicketVerdict o = ticket_verdict(p, g, tk, stored, v);
+    if (!o.g_ok) atomicOr(&flags[CW_RANGE], 1u);
+    else if (stored && !o.t_ok) atomicOr(&flags[CW_INVAL], 1u);
+    else if (o.status == RAFT_TICKET_UNKNOWN) atomicOr(&flags[CW_UNKNOWN], 1u);
+    out[m] = make_int4(o.status, o.holders, o.committed_on, o.unknown); // raft_ticket_state
 }
 
 // (the sort's configuration, SortConfig: raft_engine_impl.h)
-int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int n) {
+int propose_enqueue(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int n) {
     e->fork_needed = true;
     raft_internal_ensure_cache(e);                  // append_command reads and writes the HBM tail cache
     int bits = 1;
@@ -199,6 +166,13 @@ int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_
     else
         propose_kernel<false><<<grid, BLOCK, 0, e->stream>>>(e->dp, n, k_out, o_out, cmd, (int4*)ticket, st.dev);
     HIP_TRY(hipGetLastError());
+    return RAFT_OK;
+}
+
+// the status words of the propose enqueued last, at the head of cli
+int propose_finish(raft_engine* e) {
+    Status st;
+    st.dev = (unsigned int*)e->cli;
     if (int rc = st.fetch(e)) return rc;
     if (st.w[CW_RANGE])
         return raft_internal_fail(RAFT_ERANGE, "a proposal's group is outside the engine; nothing was applied");
@@ -207,6 +181,11 @@ int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_
                                                     " log accesses below the retained log_window: the batch's "
                                                     "results are not the reference's");
     return RAFT_OK;
+}
+
+int propose_dev(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int n) {
+    if (int rc = propose_enqueue(e, group, cmd, ticket, n)) return rc;
+    return propose_finish(e);
 }
 
 int resolve_dev(raft_engine* e, const int64_t* group, const raft_ticket* ticket, const uint32_t* cmd,
@@ -229,6 +208,12 @@ int resolve_dev(raft_engine* e, const int64_t* group, const raft_ticket* ticket,
 }
 
 }  // namespace
+
+// (raft_ticket.h: the outbox's re-propose)
+int raft_internal_propose_enqueue(raft_engine* e, const int64_t* group, const uint32_t* cmd, raft_ticket* ticket, int n) {
+    return propose_enqueue(e, group, cmd, ticket, n);
+}
+int raft_internal_propose_finish(raft_engine* e) { return propose_finish(e); }
 
 extern "C" {
 

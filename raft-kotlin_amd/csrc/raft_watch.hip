@@ -202,9 +202,13 @@ int poll(raft_engine* e, int64_t g0, int64_t n, raft_leader_event* out, int64_t 
 
 }  // namespace
 
+// raft_outbox.hip: a proposal outbox configured behind the seen pairs (it shares this allocation) is emptied
+int raft_internal_outbox_reset(raft_engine* e);
+
 // raft_engine_reset, and the first use: nothing reported yet
 int raft_internal_watch_reset(raft_engine* e) {
     if (!e->watch) return RAFT_OK;
+    if (int rc = raft_internal_outbox_reset(e)) return rc;
     const unsigned grid = (unsigned)((e->p.G + BLOCK - 1) / BLOCK);
     watch_fill_kernel<<<grid, BLOCK, 0, e->stream>>>(e->watch, e->p.G);
     HIP_TRY(hipGetLastError());

@@ -886,6 +886,100 @@ class RaftEngine:
         a = np.ascontiguousarray(a, dtype=np.int32)
         self._check(self._lib.raft_engine_write_watch(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "write_watch")
 
+    # -- the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*) ---------------------------------
+    def outbox_configure(self, capacity: int, expire_steps: int = 0):
+        """raft_engine_outbox_configure: a queue of `capacity` proposals in HBM;
+        a record older than expire_steps steps completes EXPIRED (0: never)."""
+        for name, v in (("capacity", capacity), ("expire_steps", expire_steps)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"outbox_configure: {name} {v!r} must be an integer")
+        if not (1 <= capacity < 2 ** 31 and 0 <= expire_steps < 2 ** 31):
+            raise ValueError("outbox_configure: 1 <= capacity < 2^31 and 0 <= expire_steps < 2^31")
+        self._check(self._lib.raft_engine_outbox_configure(self._h, int(capacity), int(expire_steps)), "outbox_configure")
+
+    def outbox_submit(self, groups, cmds, tags):
+        """raft_outbox_submit: enqueue proposal cmds[m] (a u32 id) for groups[m]
+        under the caller's tags[m] (int64), in batch order.  Nothing is proposed
+        before the next outbox_pump.  RAFT_EFULL / RAFT_ERANGE raise RaftError
+        and enqueue nothing."""
+        g, c = self._client_arrays(groups, cmds, "outbox_submit")
+        t = np.ascontiguousarray(tags, dtype=np.int64)
+        if t.ndim != 1 or t.shape[0] != g.shape[0]:
+            raise ValueError(f"outbox_submit: tags {t.shape} must be 1-D and as long as groups")
+        self._check(self._lib.raft_outbox_submit(self._h, C.c_void_p(g.ctypes.data), C.c_void_p(c.ctypes.data),
+                                                 C.c_void_p(t.ctypes.data), g.shape[0]), "raft_outbox_submit")
+
+    def outbox_submit_dev(self, group_ptr: int, cmd_ptr: int, tag_ptr: int, n: int, after_stream: int | None = None):
+        """raft_outbox_submit_dev: DEVICE pointers to n int64 groups, uint32
+        commands and int64 tags."""
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        self._check(self._lib.raft_outbox_submit_dev(self._h, group_ptr, cmd_ptr, tag_ptr, int(n)),
+                    "raft_outbox_submit_dev")
+
+    def _outbox_info(self, info) -> dict:
+        d = {k: int(getattr(info, k)) for k in abi.OUTBOX_INFO_FIELDS}
+        d["age_hist"] = [int(x) for x in info.age_hist]
+        return d
+
+    def outbox_len(self) -> int:
+        """Records in the outbox now (raft_engine_outbox_read's peek)."""
+        n = C.c_int64()
+        self._check(self._lib.raft_engine_outbox_read(self._h, None, 0, C.byref(n)), "outbox_read")
+        return int(n.value)
+
+    def outbox_pump(self, max_done: int | None = None):
+        """raft_engine_outbox_pump: every record gets its verdict from the
+        state the call finds; the COMMITTED and EXPIRED ones (the first
+        max_done in queue order; None: all of them) are returned as
+        abi.OUTBOX_DONE_DTYPE records and leave the queue, the ones no replica
+        holds any more are proposed again, the rest stay.  Returns (info,
+        records): info has abi.OUTBOX_INFO_FIELDS and age_hist (32 buckets).
+        RAFT_EWINDOW (a record UNKNOWN below a log_window, or a retried add
+        below one) is not raised: ``last_status`` carries the code."""
+        if max_done is None:
+            max_done = self.outbox_len()
+        if isinstance(max_done, bool) or not isinstance(max_done, (int, np.integer)) or max_done < 0:
+            raise ValueError(f"outbox_pump: max_done {max_done!r} must be an integer >= 0")
+        out = np.zeros(int(max_done), dtype=abi.OUTBOX_DONE_DTYPE)
+        n, info = C.c_int64(), abi.raft_outbox_info()
+        self._client_status(self._lib.raft_engine_outbox_pump(self._h, C.c_void_p(out.ctypes.data) if max_done else None,
+                                                              int(max_done), C.byref(n), C.byref(info)),
+                            "raft_engine_outbox_pump")
+        return self._outbox_info(info), out[: int(n.value)]
+
+    def outbox_pump_dev(self, done_ptr: int, max_done: int, after_stream: int | None = None):
+        """outbox_pump into a DEVICE buffer of max_done 32-byte records (16-byte
+        aligned); returns (info, records written)."""
+        if done_ptr % 16:
+            raise ValueError("outbox_pump_dev: the record buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        n, info = C.c_int64(), abi.raft_outbox_info()
+        self._client_status(self._lib.raft_engine_outbox_pump_dev(self._h, C.c_void_p(done_ptr), int(max_done),
+                                                                  C.byref(n), C.byref(info)),
+                            "raft_engine_outbox_pump_dev")
+        return self._outbox_info(info), int(n.value)
+
+    def outbox_read(self) -> np.ndarray:
+        """The queue in order, as abi.OUTBOX_ENTRY_DTYPE records."""
+        out = np.zeros(self.outbox_len(), dtype=abi.OUTBOX_ENTRY_DTYPE)
+        n = C.c_int64()
+        if len(out):
+            self._check(self._lib.raft_engine_outbox_read(self._h, C.c_void_p(out.ctypes.data), len(out), C.byref(n)),
+                        "outbox_read")
+        return out
+
+    def outbox_write(self, records: np.ndarray):
+        """Replace the queue with `records` (abi.OUTBOX_ENTRY_DTYPE; resuming an
+        outbox_read).  The library refuses, before storing anything, a group,
+        replica, index or status a pump would not accept."""
+        a = np.ascontiguousarray(records)
+        if a.dtype != abi.OUTBOX_ENTRY_DTYPE or a.ndim != 1:
+            raise ValueError("outbox_write: records must be a 1-D array of abi.OUTBOX_ENTRY_DTYPE")
+        self._check(self._lib.raft_engine_outbox_write(self._h, C.c_void_p(a.ctypes.data) if len(a) else None, len(a)),
+                    "outbox_write")
+
     def allreduce_counters(self, comm: RaftComm, counters_ptr: int, out_ptr: int, n_steps: int):
         """raft_engine_allreduce_counters: the sum over the ranks of n_steps
         counter rows (DEVICE pointers, [n_steps][COUNTER_STRIDE] int64; in

@@ -31,6 +31,9 @@ argument meaning and error behaviour:
 * ``RaftService.watch_leaders`` / ``newest_leader``: a leader directory kept
   up to date from the engine's leader watch -- only the groups whose leader or
   term changed since the last call cross the bus (etcd's SoftState in a Ready)
+* ``RaftService.submit_reliable`` / ``completions`` / ``pump_until_idle``: the
+  engine's proposal outbox -- commands held on the device until committed,
+  re-proposed only when no replica holds them any more, completed once
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -456,6 +459,48 @@ class RaftService:
         window).  ``last_status`` keeps the records (holders, committed_on, unknown)."""
         self.last_status = self.engine.resolve(groups, tickets, [self.commands.intern(c) for c in commands])
         return [abi.TICKET_STATUS_NAMES[s] for s in self.last_status["status"].tolist()]
+
+    # -- reliable submission: the engine's proposal outbox (Raft thesis §6.3, "the client retries") ---
+    def submit_reliable(self, groups, commands: List[str]) -> np.ndarray:
+        """Queue one command per entry of `groups` in the engine's outbox
+        (RaftEngine.outbox_configure first) and return their tags (int64, this
+        service's own running numbers).  Nothing is proposed before the next
+        completions() / pump_until_idle(): a pump proposes the new records and
+        re-proposes the ones no replica holds any more, and never one that
+        another replica might still commit, so a command commits once."""
+        n0 = getattr(self, "_next_tag", 0)
+        tags = np.arange(n0, n0 + len(commands), dtype=np.int64)
+        ids = [self.commands.intern(c) for c in commands]
+        self.engine.outbox_submit(groups, ids, tags)
+        self._next_tag = n0 + len(commands)
+        self._tag_cmd = getattr(self, "_tag_cmd", {})
+        self._tag_cmd.update(zip(tags.tolist(), ids))
+        return tags
+
+    def completions(self, max_done: Optional[int] = None) -> List[tuple]:
+        """One RaftEngine.outbox_pump: (tag, command, status, index, term, tries,
+        age) per record that completed, in queue order; status is "COMMITTED"
+        (at log[index] with `term`) or "EXPIRED" (outcome unknown, as after any
+        client timeout).  ``last_pump`` keeps the pump's info."""
+        self.last_pump, done = self.engine.outbox_pump(max_done)
+        cmd = getattr(self, "_tag_cmd", {})
+        return [(int(r["tag"]), self.commands.name(cmd.pop(int(r["tag"]))), abi.OUTBOX_DONE_NAMES[int(r["status"])],
+                 int(r["index"]), int(r["term"]), int(r["tries"]), int(r["age"])) for r in done]
+
+    def pump_until_idle(self, max_steps: int) -> List[tuple]:
+        """Step and pump until the outbox is empty or max_steps steps were
+        taken; a pump that left only PENDING records is followed by
+        assert_leadership(), since an idle group commits entries of earlier
+        terms only behind one of its leader's own.  Returns the completions."""
+        out = self.completions()
+        steps = 0
+        while self.last_pump["left"] and steps < max_steps:
+            if self.last_pump["left"] == self.last_pump["pending"]:
+                self.assert_leadership()
+            self.engine.step(1, counters=False)
+            steps += 1
+            out += self.completions()
+        return out
 
     # -- the gRPC-facing wire form (include/raft_wire.h) --------------------
     # RaftImplBase.vote()/append() (RaftServer.kt:228, :253) receive and return
