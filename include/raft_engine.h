@@ -51,8 +51,10 @@ extern "C" {
  * raft_read_serve_batch*), snapshot install (raft_engine_install_snapshot*),
  * leadership transfer (raft_transfer_batch*, raft_engine_resolve_transfers*,
  * raft_engine_evacuate*), leader no-op entries (raft_engine_append_noops*,
- * raft_engine_sm_set_noop) and the leader watch (raft_engine_poll_leaders*,
- * raft_engine_read_watch / write_watch) */
+ * raft_engine_sm_set_noop), the leader watch (raft_engine_poll_leaders*,
+ * raft_engine_read_watch / write_watch), the proposal outbox
+ * (raft_engine_outbox_*, raft_outbox_submit*) and the safety audit
+ * (raft_audit_*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -1349,6 +1351,124 @@ int raft_engine_outbox_pump_dev(raft_engine* e, raft_outbox_done* done_dev, int6
                                 raft_outbox_info* info);
 int raft_engine_outbox_read (raft_engine* e, raft_outbox_entry* out, int64_t room, int64_t* n);
 int raft_engine_outbox_write(raft_engine* e, const raft_outbox_entry* in, int64_t n);
+
+/* ---- the safety audit: Raft invariants checked over time on the device --------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * RAFT_C_DUAL_LEADER_GROUPS, raft_engine_check_log_matching and
+ * raft_engine_sm_check look at the present instant and remember nothing: none
+ * can see a committed entry that later changed or vanished, a later leader
+ * that lacks a committed entry, a replica that voted twice in a term or a term
+ * that went backwards (what RAFT_RESTART_AMNESIA does).  An audit is a ledger
+ * per group that remembers what the group has shown, and raft_audit_observe
+ * checks the state now against it.  The reference has no counterpart.
+ *
+ * - A raft_audit belongs to one engine and owns its HBM (raft_audit_device_bytes;
+ *   raft_engine_device_bytes does not count it).  The engine does not know
+ *   about it: the step kernel, the canonical state, the digest and every other
+ *   call are as before, raft_engine_reset does NOT reach it (call
+ *   raft_audit_reset), and it is destroyed before its engine.  observe and
+ *   report never write engine memory.
+ * - The ledger of one group, 8 + 2 R int32 words as raft_audit_read returns it:
+ *     [0] flags             sticky RAFT_AUDIT_* bits                         0
+ *     [1] first_step        raft_engine_step_index (low 32 bits) at the
+ *                           observe where flags first left 0                 0
+ *     [2] lead_term         the highest term in which a LEADER was observed  0
+ *     [3] lead_replica      and who                                          -1
+ *     [4] anchor_count  C   the longest committed prefix any replica showed  0
+ *     [5] anchor_term       the entry at index C - 1 when C was recorded     0
+ *     [6] anchor_cmd                                                         0
+ *     [7] anchor_seen_term  the highest currentTerm in the group at the
+ *                           observe that recorded C                          0
+ *     [8 + 2r], [9 + 2r]    replica r's currentTerm, votedFor as last
+ *                           observed                                         0, -1
+ *   (last column: the zero state of create and reset).
+ * - One observe of one group, in this order; "old" is the ledger before the
+ *   call, hi_r = min(commitIndex_r, lastIndex_r) within 0..log_cap:
+ *   1. per replica r: term_r < old term -> TERM_REGRESSED; term_r == old term,
+ *      old votedFor >= 0 and voted_r != old votedFor -> VOTE_CHANGED; then the
+ *      pair is stored.
+ *   2. two replicas LEADER now with equal terms -> TWO_LEADERS; a replica r
+ *      LEADER now with term_r == old lead_term, old lead_replica >= 0 and
+ *      r != old lead_replica -> TWO_LEADERS; then the newest leader
+ *      (raft_read_begin_batch's rule) is stored if its term > old lead_term.
+ *   3. when old C > 0, with i = C - 1: every replica with hi_r >= C must hold
+ *      (anchor_term, anchor_cmd) at i, else COMMIT_CHANGED (State Machine
+ *      Safety over time); every replica LEADER now with term_r > old
+ *      anchor_seen_term must have lastIndex_r >= C and hold the anchor at i,
+ *      else LEADER_INCOMPLETE (Leader Completeness).  The term guard makes
+ *      that sound: the anchor was committed in a term <= anchor_seen_term, and
+ *      a stale leader of a lower term, still LEADER while isolated, may lack
+ *      it (Figure 8 of the Raft paper).  With a log_window a slot below a
+ *      replica's window (i < physLen_r - W) is not read: that check is skipped
+ *      and counted in `unknown`, once per skipped check.
+ *   4. C' = max_r hi_r.  If C' > C, the lowest r with hi_r == C' gives the new
+ *      anchor (C', its entry at C' - 1) and anchor_seen_term = max_r term_r;
+ *      if that slot is below its window, one `unknown` and the old anchor
+ *      stays.  A smaller C' is normal (a restart sets commitIndex to 0, quirk
+ *      Q4 lowers it) and raises nothing.
+ *   5. the bits raised are OR-ed into flags; first_step is stored when flags
+ *      leaves 0.
+ * - raft_audit_report lists the groups of the range with flags != 0 in
+ *   ascending group order, cut at max_events; `pending` counts the rest.  It
+ *   consumes nothing: the same call returns the same records.  max_events == 0
+ *   (with or without a buffer) is a peek.
+ * - raft_audit_write resumes a ledger.  RAFT_EINVAL with nothing stored:
+ *   unknown flag bits, lead_replica outside -1..R-1, anchor_count outside
+ *   0..log_cap.  No other word is ever used as an index.
+ * RAFT_EINVAL: null handle or info, max_events < 0, out == NULL with
+ * max_events > 0, a _dev buffer that is not 16-byte aligned; RAFT_ERANGE:
+ * groups outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Both protocol modes and every log layout.  Promised: in RAFT_MODE_TEXTBOOK
+ * on persistent logs (no RAFT_RESTART_AMNESIA) no flag is ever raised, whatever
+ * the faults, restarts, installs, transfers, no-ops and outbox traffic and
+ * however rarely observe is called.  In reference mode and after an amnesia
+ * restart the flags are observations about the protocol, as with
+ * raft_engine_check_log_matching.  The rules see sampled instants: no flag
+ * does not prove that nothing happened between two observes.
+ *
+ * Ordering is raft_engine_drain_committed's: every call runs on the engine
+ * stream, sees every step enqueued before it, later step launches wait for
+ * it, and it returns when its kernels have finished. */
+#define RAFT_AUDIT_TERM_REGRESSED    (1 << 0)  /* a replica's currentTerm went backwards */
+#define RAFT_AUDIT_VOTE_CHANGED      (1 << 1)  /* a replica changed its vote within a term */
+#define RAFT_AUDIT_TWO_LEADERS       (1 << 2)  /* two leaders of one term, at once or across observes */
+#define RAFT_AUDIT_COMMIT_CHANGED    (1 << 3)  /* a committed entry changed */
+#define RAFT_AUDIT_LEADER_INCOMPLETE (1 << 4)  /* a newer leader lacks a committed entry */
+typedef struct raft_audit raft_audit;
+typedef struct raft_audit_info {         /* 64 bytes */
+    int64_t newly_flagged;     /* groups whose flags went from 0 to nonzero in this call */
+    int64_t flagged;           /* groups of the range with flags != 0 after it */
+    int64_t term_regressed;    /* groups that gained the bit in this call, per kind */
+    int64_t vote_changed;
+    int64_t two_leaders;
+    int64_t commit_changed;
+    int64_t leader_incomplete;
+    int64_t unknown;           /* checks skipped below a log_window */
+} raft_audit_info;
+typedef struct raft_audit_event {        /* 16 bytes */
+    int64_t group;             /* engine-local group index */
+    int32_t flags;
+    int32_t first_step;
+} raft_audit_event;
+typedef struct raft_audit_report_info {  /* 64 bytes */
+    int64_t delivered;         /* events written to out */
+    int64_t pending;           /* flagged groups beyond max_events (all of them, in a peek) */
+    int64_t flagged;           /* delivered + pending */
+    int64_t reserved[5];       /* 0 */
+} raft_audit_report_info;
+int raft_audit_create (raft_engine* e, raft_audit** out);
+int raft_audit_destroy(raft_audit* a);
+int raft_audit_reset  (raft_audit* a);
+int64_t raft_audit_device_bytes(raft_audit* a);
+int raft_audit_observe(raft_audit* a, int64_t g0, int64_t n, raft_audit_info* info);
+int raft_audit_report    (raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out_host, int64_t max_events,
+                          raft_audit_report_info* info);
+int raft_audit_report_dev(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out_dev, int64_t max_events,
+                          raft_audit_report_info* info);
+int raft_audit_read (raft_audit* a, int64_t g0, int64_t n, int32_t* out);
+int raft_audit_write(raft_audit* a, int64_t g0, int64_t n, const int32_t* in);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

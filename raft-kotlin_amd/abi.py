@@ -353,6 +353,38 @@ OUTBOX_NEW, OUTBOX_COMMITTED, OUTBOX_EXPIRED = -1, 1, 2
 OUTBOX_DONE_NAMES = {1: "COMMITTED", 2: "EXPIRED"}
 
 
+class raft_audit_info(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("newly_flagged", "flagged", "term_regressed", "vote_changed", "two_leaders",
+                                         "commit_changed", "leader_incomplete", "unknown")]
+
+
+class raft_audit_event(C.Structure):
+    _fields_ = [("group", C.c_int64), ("flags", C.c_int32), ("first_step", C.c_int32)]
+
+
+class raft_audit_report_info(C.Structure):
+    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("flagged", C.c_int64), ("reserved", C.c_int64 * 5)]
+
+
+# the safety audit (raft_audit_*): the sticky flag bits in the order of raft_audit_info's per-kind counts,
+# raft_audit_event as a numpy record (16 bytes, no padding), the words of a group's exported ledger
+AUDIT_TERM_REGRESSED, AUDIT_VOTE_CHANGED, AUDIT_TWO_LEADERS, AUDIT_COMMIT_CHANGED, AUDIT_LEADER_INCOMPLETE = \
+    1, 2, 4, 8, 16
+AUDIT_KINDS = ("term_regressed", "vote_changed", "two_leaders", "commit_changed", "leader_incomplete")
+AUDIT_ALL = 31
+AUDIT_INFO_FIELDS = ("newly_flagged", "flagged") + AUDIT_KINDS + ("unknown",)
+AUDIT_REPORT_FIELDS = ("delivered", "pending", "flagged")
+AUDIT_EVENT_DTYPE = np.dtype([("group", np.int64), ("flags", np.int32), ("first_step", np.int32)])
+AUDIT_WORDS = ("flags", "first_step", "lead_term", "lead_replica", "anchor_count", "anchor_term", "anchor_cmd",
+               "anchor_seen_term")
+AUDIT_HEAD = len(AUDIT_WORDS)
+
+
+def audit_words(R: int) -> int:
+    """int32 words of one group's exported ledger (raft_audit_read)."""
+    return AUDIT_HEAD + 2 * R
+
+
 # the reference's hard-coded constants (SURVEY.md §6)
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -536,6 +568,15 @@ def load_library(path: str | None = None):
         "raft_engine_outbox_pump_dev": (C.c_int, [eng, C.c_void_p, I64, P(I64), P(raft_outbox_info)]),
         "raft_engine_outbox_read": (C.c_int, [eng, C.c_void_p, I64, P(I64)]),
         "raft_engine_outbox_write": (C.c_int, [eng, C.c_void_p, I64]),
+        "raft_audit_create": (C.c_int, [eng, P(C.c_void_p)]),
+        "raft_audit_destroy": (C.c_int, [C.c_void_p]),
+        "raft_audit_reset": (C.c_int, [C.c_void_p]),
+        "raft_audit_device_bytes": (I64, [C.c_void_p]),
+        "raft_audit_observe": (C.c_int, [C.c_void_p, I64, I64, P(raft_audit_info)]),
+        "raft_audit_report": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p, I64, P(raft_audit_report_info)]),
+        "raft_audit_report_dev": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p, I64, P(raft_audit_report_info)]),
+        "raft_audit_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
+        "raft_audit_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -601,6 +642,8 @@ EXPORTED_SYMBOLS = [
     "raft_engine_poll_leaders", "raft_engine_poll_leaders_dev", "raft_engine_read_watch", "raft_engine_write_watch",
     "raft_engine_outbox_configure", "raft_outbox_submit", "raft_outbox_submit_dev", "raft_engine_outbox_pump",
     "raft_engine_outbox_pump_dev", "raft_engine_outbox_read", "raft_engine_outbox_write",
+    "raft_audit_create", "raft_audit_destroy", "raft_audit_reset", "raft_audit_device_bytes", "raft_audit_observe",
+    "raft_audit_report", "raft_audit_report_dev", "raft_audit_read", "raft_audit_write",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

@@ -1,0 +1,455 @@
+// raft_audit.hip — the safety audit (include/raft_engine.h raft_audit_*): a
+// ledger per group, in HBM of its own behind a handle of its own, that
+// remembers what the group has shown -- every replica's (currentTerm,
+// votedFor), the newest leader seen, the longest committed prefix seen and the
+// entry at its end -- and an observe between two step launches that checks
+// the state now against it: a term that went backwards, a vote changed within
+// a term, two leaders of one term (at once, or across two observes), a
+// committed entry that changed, a newer leader that lacks it.  The reference
+// has no counterpart.
+//
+// A side path with kernels of its own: observe reads quads 0 and 1 and
+// commitIndex of each replica and at most two 8-byte log slots per group, and
+// writes only the ledger; report reads only the ledger.  Neither writes engine
+// memory.
+//   observe   eight lanes per group (raft_ticket.h's shape: 32 groups per
+//             256-thread block), lane r < R is replica r.  Group-level
+//             decisions go through __shfl_xor over the eight lanes and through
+//             the group's byte of a ballot; lane 0 stores the header.  The
+//             counts of a call go through ballots into a stripe (one atomic per
+//             nonzero word and wave).
+//   report    the watch's three passes with the predicate flags != 0: flag
+//             (per-wave counts), an exclusive scan of them (rocprim), a staged
+//             contiguous write of 16-byte records.  The order of the records
+//             comes from the scan, never from an atomic.  Passes 2 and 3 run
+//             only when something is delivered.
+// The ledger on the device: hdr, two int4 per group (flags, first_step,
+// lead_term, lead_replica | anchor_count, anchor_term, anchor_cmd,
+// anchor_seen_term), and pairs, one int2 (currentTerm, votedFor) per replica at
+// g * R + r -- a wave's 32 groups read one contiguous run of each.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <algorithm>
+#include <climits>
+#include <string>
+#include <vector>
+
+#include "raft_engine_impl.h"
+
+using namespace raft;
+
+struct raft_audit {
+    raft_engine* e;
+    char* mem;                  // one allocation: hdr [G] of 32 bytes, then pairs [G * R] of 8 bytes
+    size_t bytes;
+    int4* hdr;
+    int2* pairs;
+};
+
+namespace {
+
+static_assert(sizeof(raft_audit_event) == 16 && sizeof(raft_audit_info) == 64 && sizeof(raft_audit_report_info) == 64,
+              "record layouts of the C-ABI");
+static_assert(RAFT_MAX_R == 8, "eight lanes per group");
+
+constexpr uint32_t AUDIT_ALL = RAFT_AUDIT_TERM_REGRESSED | RAFT_AUDIT_VOTE_CHANGED | RAFT_AUDIT_TWO_LEADERS |
+                               RAFT_AUDIT_COMMIT_CHANGED | RAFT_AUDIT_LEADER_INCOMPLETE;
+
+// the counts of an observe, striped as a restart's totals, at the head of aux; a report uses word 0 alone
+enum { AW_NEWLY = 0, AW_FLAGGED, AW_TERM, AW_VOTE, AW_TWO, AW_COMMIT, AW_LEADER, AW_UNKNOWN, AW_WORDS };
+using Counts = DevWords<unsigned long long, HDR_STRIPES, HDR_LINE, AW_WORDS, true>;
+
+// over the eight lanes of a group (every lane of the wave takes part)
+__device__ __forceinline__ int32_t group_max(int32_t v) {
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ long long group_max64(long long v) {
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t group_or(uint32_t v) {
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) v |= __shfl_xor(v, d, 64);
+    return v;
+}
+// the group's byte of a ballot: bit r is its lane r
+__device__ __forceinline__ uint32_t group_bits(unsigned long long ballot) {
+    return (uint32_t)(ballot >> (threadIdx.x & 56)) & 0xFFu;
+}
+__device__ __forceinline__ bool differ(int4 a, int4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; }
+
+__global__ __launch_bounds__(BLOCK) void audit_fill_kernel(int4* __restrict__ hdr, int2* __restrict__ pairs, int64_t g0,
+                                                           int64_t n, int R) {
+    const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j < n) {
+        hdr[2 * (g0 + j)] = make_int4(0, 0, 0, -1);
+        hdr[2 * (g0 + j) + 1] = make_int4(0, 0, 0, 0);
+    }
+    if (j < n * R) pairs[g0 * R + j] = make_int2(0, -1);
+}
+
+// One observe of groups [g0, g0 + n): the five steps of include/raft_engine.h,
+// in their order.  Lanes of a group beyond R and groups beyond the range load
+// at a clamped index, take part in the shuffles and store nothing.
+__global__ __launch_bounds__(BLOCK) void audit_observe_kernel(DevParams p, int4* __restrict__ hdr,
+                                                              int2* __restrict__ pairs, int64_t g0, int64_t n,
+                                                              int32_t step, unsigned long long* cnt) {
+    const int64_t j = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 3;
+    const int r = threadIdx.x & 7, R = p.R;
+    const bool live = j < n;
+    const int64_t g = g0 + (live ? j : n - 1);                          // g0 <= g < g0 + n <= G (check_groups)
+    const bool act = live && r < R;
+    const int64_t idx = g * R + min(r, R - 1);
+    const int4 q0 = *quad(p, 0, idx);                                   // term, votedFor, role
+    const int4 q1 = *quad(p, 1, idx);                                   // lastIndex, physLen
+    const int32_t commit = quad(p, 2, idx)->x;
+    const int2 old = pairs[idx];
+    const int4 H0 = hdr[2 * g], H1 = hdr[2 * g + 1];                    // the group's eight lanes read one sector
+    const int32_t term = q0.x, voted = q0.y, last = q1.x, phys = q1.y;
+    const bool leader = act && q0.z == RAFT_LEADER;
+    const bool ring = p.W != FLAT_W;
+    uint32_t bits = 0;
+
+    // 1. term and vote
+    if (act && term < old.x) bits |= RAFT_AUDIT_TERM_REGRESSED;
+    if (act && term == old.x && old.y >= 0 && voted != old.y) bits |= RAFT_AUDIT_VOTE_CHANGED;
+    if (act && (term != old.x || voted != old.y)) pairs[idx] = make_int2(term, voted);
+
+    // 2. Election Safety: now, and against the leader on record
+    const uint32_t lbits = group_bits(__ballot(leader));
+    bool twin = false;
+#pragma unroll
+    for (int d = 1; d < 8; ++d) {
+        const int32_t to = __shfl_xor(term, d, 64);
+        twin |= ((lbits >> (r ^ d)) & 1u) && to == term;
+    }
+    if (leader && (twin || (term == H0.z && H0.w >= 0 && r != H0.w))) bits |= RAFT_AUDIT_TWO_LEADERS;
+    // find_newest_leader's rule: the highest term, the lowest index among equals
+    const long long none = LLONG_MIN;
+    const long long key = group_max64(leader ? (long long)term * 8 + (7 - r) : none);
+    int32_t lead_term = H0.z, lead_rep = H0.w;
+    if (key != none && (int32_t)(key >> 3) > lead_term) {
+        lead_term = (int32_t)(key >> 3);
+        lead_rep = 7 - (int32_t)(key & 7);
+    }
+
+    // 3. the anchor: slot C - 1, read only after the bounds and window tests
+    const int32_t C = H1.x, hi = committed_hi(p, commit, last);
+    bool unk_a = false, unk_b = false;
+    if (C > 0) {
+        const int32_t i = C - 1;
+        const bool below = ring && i < phys - p.W;
+        const bool need_a = act && hi >= C;                             // (then i < lastIndex)
+        const bool newer = leader && term > H1.w;
+        const bool need_b = newer && last >= C;
+        if (newer && last < C) bits |= RAFT_AUDIT_LEADER_INCOMPLETE;
+        unk_a = need_a && below;
+        unk_b = need_b && below;
+        if ((need_a || need_b) && !below && i < p.cap) {
+            const uint2 en = *log_of(p, idx).at<true>(i);
+            if ((int32_t)en.x != H1.y || en.y != (uint32_t)H1.z)
+                bits |= (need_a ? RAFT_AUDIT_COMMIT_CHANGED : 0u) | (need_b ? RAFT_AUDIT_LEADER_INCOMPLETE : 0u);
+        }
+    }
+
+    // 4. advance: the second slot read only in the one lane of a group that advances
+    const int32_t Cn = group_max(act ? hi : 0);
+    const bool adv = Cn > C;
+    const uint32_t hbits = group_bits(__ballot(act && hi == Cn));
+    const int rs = hbits ? __ffs(hbits) - 1 : 0;
+    const bool mine = adv && act && r == rs;
+    const bool below_n = ring && Cn - 1 < phys - p.W;
+    uint2 en2 = make_uint2(0u, 0u);
+    if (mine && !below_n) en2 = *log_of(p, idx).at<true>(Cn - 1);       // Cn - 1 < hi <= min(lastIndex, log_cap)
+    const bool unk_n = mine && below_n;
+    const int32_t seen_term = group_max(act ? term : INT_MIN);
+    const int src = (threadIdx.x & 56) | rs;
+    const uint32_t e2t = __shfl(en2.x, src, 64), e2c = __shfl(en2.y, src, 64);
+    const bool skip = __shfl((int)below_n, src, 64) != 0;
+    int4 N1 = H1;
+    if (adv && !skip) N1 = make_int4(Cn, (int32_t)e2t, (int32_t)e2c, seen_term);
+
+    // 5. sticky flags, the step of the first one
+    const uint32_t was = (uint32_t)H0.x, now = was | group_or(bits);
+    const bool head = live && r == 0;
+    const bool newly = was == 0 && now != 0;
+    const int4 N0 = make_int4((int32_t)now, newly ? step : H0.y, lead_term, lead_rep);
+    if (head && differ(N0, H0)) hdr[2 * g] = N0;
+    if (head && differ(N1, H1)) hdr[2 * g + 1] = N1;
+
+    const uint32_t got = head ? now & ~was : 0u;
+    const unsigned long long b_new = __ballot(head && newly), b_fl = __ballot(head && now != 0),
+                             b_t = __ballot(got & RAFT_AUDIT_TERM_REGRESSED), b_v = __ballot(got & RAFT_AUDIT_VOTE_CHANGED),
+                             b_2 = __ballot(got & RAFT_AUDIT_TWO_LEADERS), b_c = __ballot(got & RAFT_AUDIT_COMMIT_CHANGED),
+                             b_l = __ballot(got & RAFT_AUDIT_LEADER_INCOMPLETE);
+    const uint32_t unk = (uint32_t)(__popcll(__ballot(unk_a)) + __popcll(__ballot(unk_b)) + __popcll(__ballot(unk_n)));
+    if ((threadIdx.x & 63) == 0) {
+        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+        unsigned long long* line = cnt + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
+        if (b_new) atomicAdd(line + AW_NEWLY, (unsigned long long)__popcll(b_new));
+        if (b_fl) atomicAdd(line + AW_FLAGGED, (unsigned long long)__popcll(b_fl));
+        if (b_t) atomicAdd(line + AW_TERM, (unsigned long long)__popcll(b_t));
+        if (b_v) atomicAdd(line + AW_VOTE, (unsigned long long)__popcll(b_v));
+        if (b_2) atomicAdd(line + AW_TWO, (unsigned long long)__popcll(b_2));
+        if (b_c) atomicAdd(line + AW_COMMIT, (unsigned long long)__popcll(b_c));
+        if (b_l) atomicAdd(line + AW_LEADER, (unsigned long long)__popcll(b_l));
+        if (unk) atomicAdd(line + AW_UNKNOWN, (unsigned long long)unk);
+    }
+}
+
+// report, pass 1.  wcnt[w]: flagged groups among groups [64 w, 64 w + 64) of the range
+__global__ __launch_bounds__(BLOCK) void audit_flag_kernel(const int4* __restrict__ hdr, int64_t g0, int64_t n,
+                                                           uint32_t* __restrict__ wcnt, unsigned long long* cnt) {
+    const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = j < n;
+    const int64_t g = g0 + (live ? j : n - 1);
+    const unsigned long long b = __ballot(live && hdr[2 * g].x != 0);
+    if ((threadIdx.x & 63) == 0 && live) {                              // lane 0 live: the wave is inside the range
+        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+        wcnt[wave] = (uint32_t)__popcll(b);
+        if (b) atomicAdd(cnt + (wave & (HDR_STRIPES - 1)) * HDR_LINE, (unsigned long long)__popcll(b));
+    }
+}
+
+struct CountToOffset {
+    __host__ __device__ unsigned long long operator()(uint32_t c) const { return c; }
+};
+
+// report, pass 3.  Wave w owns groups [64 w, 64 w + 64) of the range and the
+// output slots [off[w], off[w] + wcnt[w]), cut at max_events.
+__global__ __launch_bounds__(BLOCK) void audit_write_kernel(const int4* __restrict__ hdr, int64_t g0, int64_t n,
+                                                            const uint32_t* __restrict__ wcnt,
+                                                            const unsigned long long* __restrict__ off,
+                                                            uint4* __restrict__ out, int64_t max_events) {
+    __shared__ uint4 stage[WAVES_PER_BLOCK][64];                       // 64 records of 16 bytes per wave
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
+    const int64_t j0 = wave * 64;
+    if (j0 >= n) return;                                               // wave-uniform
+    const uint32_t c = wcnt[wave];
+    const unsigned long long base = off[wave], room = (unsigned long long)max_events;
+    if (c == 0 || base >= room) return;                                // wave-uniform: nothing of this wave is written
+    const uint32_t take = (uint32_t)min((unsigned long long)c, room - base);
+    const int64_t j = j0 + lane;
+    const bool live = j < n;
+    const int64_t g = g0 + (live ? j : n - 1);
+    const int4 H0 = hdr[2 * g];
+    const bool f = live && H0.x != 0;
+    // the ledger is the flag pass's: the ballot has c bits, so every rank is below 64
+    const uint32_t rank = (uint32_t)__popcll(__ballot(f) & ((1ull << lane) - 1ull));
+    uint4* st = stage[wv];
+    if (f && rank < take)
+        st[rank] = make_uint4((uint32_t)((uint64_t)g & 0xFFFFFFFFu), (uint32_t)((uint64_t)g >> 32), (uint32_t)H0.x,
+                              (uint32_t)H0.y);
+    // the wave's own LDS accesses complete in order: only the compiler must keep them so
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if ((uint32_t)lane < take) out[base + lane] = st[lane];            // base + take <= max_events: inside out
+}
+
+int check_audit(raft_audit* a, int64_t g0, int64_t n) {
+    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
+    return check_groups(a->e, g0, n);
+}
+
+// the zero state of groups [g0, g0 + n), enqueued on the engine stream
+int fill(raft_audit* a, int64_t g0, int64_t n) {
+    const int R = a->e->p.R;
+    const unsigned grid = (unsigned)((n * R + BLOCK - 1) / BLOCK);
+    audit_fill_kernel<<<grid, BLOCK, 0, a->e->stream>>>(a->hdr, a->pairs, g0, n, R);
+    HIP_TRY(hipGetLastError());
+    return RAFT_OK;
+}
+
+int report(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out, int64_t max_events,
+           raft_audit_report_info* info, bool out_on_host) {
+    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
+    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
+    *info = raft_audit_report_info{};
+    raft_engine* e = a->e;
+    if (int rc = check_groups(e, g0, n)) return rc;
+    if (max_events < 0) return raft_internal_fail(RAFT_EINVAL, "max_events must be >= 0");
+    if (!out && max_events > 0) return raft_internal_fail(RAFT_EINVAL, "null record buffer with max_events > 0");
+    if (!out_on_host && !aligned16(out)) return raft_internal_fail(RAFT_EINVAL, "the record buffer must be 16-byte aligned");
+    if (n == 0) return RAFT_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    e->fork_needed = true;
+    const size_t nwaves = (size_t)((n + 63) / 64);
+    const auto counts_of = [](uint32_t* c) { return rocprim::make_transform_iterator(c, CountToOffset{}); };
+    size_t scan_b = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, counts_of(nullptr), (unsigned long long*)nullptr, 0ull, nwaves,
+                                    rocprim::plus<unsigned long long>(), e->stream));
+    const size_t cnt_b = al256(nwaves * 4), off_b = al256(nwaves * 8);
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Counts::BYTES + cnt_b + off_b + al256(scan_b)))
+        return rc;
+    uint32_t* wcnt = (uint32_t*)(e->aux + Counts::BYTES);
+    unsigned long long* off = (unsigned long long*)(e->aux + Counts::BYTES + cnt_b);
+    void* scan_tmp = e->aux + Counts::BYTES + cnt_b + off_b;
+    Counts c;
+    if (int rc = c.zero(e, e->aux)) return rc;
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    audit_flag_kernel<<<grid, BLOCK, 0, e->stream>>>(a->hdr, g0, n, wcnt, c.dev);
+    HIP_TRY(hipGetLastError());
+    if (int rc = c.fetch(e)) return rc;
+    const int64_t total = (int64_t)c.w[0];
+    const int64_t delivered = out ? std::min(total, max_events) : 0;
+    info->delivered = delivered;
+    info->pending = total - delivered;
+    info->flagged = total;
+    if (delivered == 0) return RAFT_OK;
+    uint4* dst = (uint4*)out;
+    if (out_on_host) {
+        if (int rc = raft_internal_grow_dev(e, &e->apo, &e->apo_bytes, (size_t)delivered * sizeof(raft_audit_event)))
+            return rc;
+        dst = (uint4*)e->apo;
+    }
+    HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_b, counts_of(wcnt), off, 0ull, nwaves,
+                                    rocprim::plus<unsigned long long>(), e->stream));
+    HIP_TRY(hipGetLastError());
+    audit_write_kernel<<<grid, BLOCK, 0, e->stream>>>(a->hdr, g0, n, wcnt, off, dst, max_events);
+    HIP_TRY(hipGetLastError());
+    if (out_on_host)
+        HIP_TRY(hipMemcpyAsync(out, dst, (size_t)delivered * sizeof(raft_audit_event), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return RAFT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int raft_audit_create(raft_engine* e, raft_audit** out) {
+    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
+    if (!out) return raft_internal_fail(RAFT_EINVAL, "null out");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(e->device));
+    raft_audit* a = new raft_audit{};
+    a->e = e;
+    const size_t hdr_b = al256((size_t)e->p.G * 32), pair_b = al256((size_t)e->dp.GR * 8);
+    if (hipMalloc((void**)&a->mem, hdr_b + pair_b) != hipSuccess) {
+        delete a;
+        return raft_internal_fail(RAFT_ENOMEM, "the audit's ledger: hipMalloc failed");
+    }
+    a->bytes = hdr_b + pair_b;
+    a->hdr = (int4*)a->mem;
+    a->pairs = (int2*)(a->mem + hdr_b);
+    if (int rc = raft_audit_reset(a)) {
+        (void)hipFree(a->mem);
+        delete a;
+        return rc;
+    }
+    *out = a;
+    return RAFT_OK;
+}
+
+int raft_audit_destroy(raft_audit* a) {
+    if (!a) return RAFT_OK;
+    if (a->e) {
+        (void)hipSetDevice(a->e->device);
+        (void)hipStreamSynchronize(a->e->stream);
+    }
+    (void)hipFree(a->mem);
+    delete a;
+    return RAFT_OK;
+}
+
+int raft_audit_reset(raft_audit* a) {
+    if (int rc = check_audit(a, 0, 0)) return rc;
+    raft_engine* e = a->e;
+    HIP_TRY(hipSetDevice(e->device));
+    e->fork_needed = true;
+    if (int rc = fill(a, 0, e->p.G)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return RAFT_OK;
+}
+
+int64_t raft_audit_device_bytes(raft_audit* a) { return a ? (int64_t)a->bytes : 0; }
+
+int raft_audit_observe(raft_audit* a, int64_t g0, int64_t n, raft_audit_info* info) {
+    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
+    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
+    *info = raft_audit_info{};
+    raft_engine* e = a->e;
+    if (int rc = check_groups(e, g0, n)) return rc;
+    if (n == 0) return RAFT_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    e->fork_needed = true;                           // later step launches wait for these reads of the state
+    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Counts::BYTES)) return rc;
+    Counts c;
+    if (int rc = c.zero(e, e->aux)) return rc;
+    const unsigned grid = (unsigned)((n * 8 + BLOCK - 1) / BLOCK);
+    audit_observe_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, a->hdr, a->pairs, g0, n, (int32_t)(uint32_t)e->t, c.dev);
+    HIP_TRY(hipGetLastError());
+    if (int rc = c.fetch(e)) return rc;
+    info->newly_flagged = (int64_t)c.w[AW_NEWLY];
+    info->flagged = (int64_t)c.w[AW_FLAGGED];
+    info->term_regressed = (int64_t)c.w[AW_TERM];
+    info->vote_changed = (int64_t)c.w[AW_VOTE];
+    info->two_leaders = (int64_t)c.w[AW_TWO];
+    info->commit_changed = (int64_t)c.w[AW_COMMIT];
+    info->leader_incomplete = (int64_t)c.w[AW_LEADER];
+    info->unknown = (int64_t)c.w[AW_UNKNOWN];
+    return RAFT_OK;
+}
+
+int raft_audit_report(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out_host, int64_t max_events,
+                      raft_audit_report_info* info) {
+    return report(a, g0, n, out_host, max_events, info, true);
+}
+
+int raft_audit_report_dev(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out_dev, int64_t max_events,
+                          raft_audit_report_info* info) {
+    return report(a, g0, n, out_dev, max_events, info, false);
+}
+
+int raft_audit_read(raft_audit* a, int64_t g0, int64_t n, int32_t* out) {
+    if (int rc = check_audit(a, g0, n)) return rc;
+    if (n == 0) return RAFT_OK;
+    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
+    raft_engine* e = a->e;
+    const int R = e->p.R, W = 8 + 2 * R;
+    std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(h.data(), a->hdr + 2 * g0, h.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(pr.data(), a->pairs + g0 * R, pr.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int64_t k = 0; k < n; ++k) {
+        std::memcpy(out + k * W, h.data() + k * 8, 32);
+        std::memcpy(out + k * W + 8, pr.data() + k * R * 2, (size_t)R * 8);
+    }
+    return RAFT_OK;
+}
+
+int raft_audit_write(raft_audit* a, int64_t g0, int64_t n, const int32_t* in) {
+    if (int rc = check_audit(a, g0, n)) return rc;
+    if (n == 0) return RAFT_OK;
+    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
+    raft_engine* e = a->e;
+    const int R = e->p.R, W = 8 + 2 * R;
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t* w = in + k * W;
+        if ((uint32_t)w[0] & ~AUDIT_ALL) return raft_internal_fail(RAFT_EINVAL, "a ledger's flags hold unknown bits");
+        if (w[3] < -1 || w[3] >= R) return raft_internal_fail(RAFT_EINVAL, "a ledger's lead_replica must be in -1..R-1");
+        if (w[4] < 0 || w[4] > e->p.log_cap)
+            return raft_internal_fail(RAFT_EINVAL, "a ledger's anchor_count must be in 0..log_cap");
+    }
+    std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
+    for (int64_t k = 0; k < n; ++k) {
+        std::memcpy(h.data() + k * 8, in + k * W, 32);
+        std::memcpy(pr.data() + k * R * 2, in + k * W + 8, (size_t)R * 8);
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    e->fork_needed = true;
+    HIP_TRY(hipMemcpyAsync(a->hdr + 2 * g0, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(a->pairs + g0 * R, pr.data(), pr.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return RAFT_OK;
+}
+
+}  // extern "C"

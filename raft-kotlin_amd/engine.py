@@ -13,6 +13,7 @@ library and a missing library or device raises.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -60,6 +61,127 @@ class RaftComm:
             pass
 
 
+class RaftAudit:
+    """A safety audit of one engine (include/raft_engine.h raft_audit_*): a
+    ledger per group in HBM of its own, and `observe`, which checks the state
+    now against it -- a term that went backwards, a vote changed within a
+    term, two leaders of one term, a committed entry that changed, a newer
+    leader that lacks it.  Made by RaftEngine.audit(); close it before its
+    engine.  RaftEngine.reset does not reach it: call reset() here."""
+
+    def __init__(self, engine: "RaftEngine"):
+        self._lib, self.engine = engine._lib, engine
+        self.R, self.G = engine.R, engine.G
+        self.words = abi.audit_words(self.R)
+        h = C.c_void_p()
+        engine._check(self._lib.raft_audit_create(engine._h, C.byref(h)), "raft_audit_create")
+        self._h = h
+
+    def _check(self, rc: int, what: str):
+        if rc != abi.RAFT_OK:
+            raise RaftError(f"{what} failed ({rc}): " + self._lib.raft_last_error().decode(errors="replace"))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.raft_audit_destroy(self._h)                     # (RaftEngine.close closes its audits first)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _range(self, g0, n, what: str):
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
+        return int(g0), int(n)
+
+    @property
+    def device_bytes(self) -> int:
+        """HBM owned by the audit (RaftEngine.device_bytes does not count it)."""
+        return int(self._lib.raft_audit_device_bytes(self._h))
+
+    def reset(self):
+        """Every ledger back to its zero state (as created)."""
+        self._check(self._lib.raft_audit_reset(self._h), "audit reset")
+
+    def observe(self, g0: int = 0, n: int | None = None) -> dict:
+        """raft_audit_observe of groups [g0, g0 + n): check the state now
+        against the ledger and advance the ledger.  Returns newly_flagged,
+        flagged, one count per kind (abi.AUDIT_KINDS) of the groups that gained
+        that bit in this call, and unknown (checks skipped below a log_window)."""
+        g0, n = self._range(g0, n, "observe")
+        ai = abi.raft_audit_info()
+        self._check(self._lib.raft_audit_observe(self._h, g0, n, C.byref(ai)), "raft_audit_observe")
+        return {k: int(getattr(ai, k)) for k in abi.AUDIT_INFO_FIELDS}
+
+    def _report(self, fn, g0, n, out_ptr, room, what: str) -> dict:
+        ri = abi.raft_audit_report_info()
+        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(ri)), what)
+        return {k: int(getattr(ri, k)) for k in abi.AUDIT_REPORT_FIELDS}
+
+    @staticmethod
+    def _room(max_events, what: str):
+        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
+                                       or max_events < 0):
+            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
+
+    def report(self, g0: int = 0, n: int | None = None, max_events: int | None = None):
+        """raft_audit_report: (info, events) -- the groups of [g0, g0 + n) with
+        flags != 0 as a numpy array of abi.AUDIT_EVENT_DTYPE (group, flags,
+        first_step) in ascending group order, at most max_events of them (None:
+        all of them; 0: a peek).  info: delivered, pending, flagged.  Nothing
+        is consumed: the same call returns the same events."""
+        g0, n = self._range(g0, n, "report")
+        self._room(max_events, "report")
+        fn = self._lib.raft_audit_report
+        if max_events is None:
+            max_events = self._report(fn, g0, n, 0, 0, "raft_audit_report")["pending"]
+        out = np.zeros(max(1, int(max_events)), dtype=abi.AUDIT_EVENT_DTYPE)
+        info = self._report(fn, g0, n, out.ctypes.data, int(max_events), "raft_audit_report")
+        return info, out[: info["delivered"]]
+
+    def report_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None) -> dict:
+        """report into a DEVICE buffer of max_events 16-byte records (16-byte
+        aligned); returns the info once the kernels finished."""
+        g0, n = self._range(g0, n, "report_dev")
+        self._room(max_events, "report_dev")
+        if max_events is None or (max_events > 0 and not out_ptr):
+            raise ValueError("report_dev: a device buffer and its max_events are required")
+        if out_ptr % 16:
+            raise ValueError("report_dev: the record buffer must be 16-byte aligned")
+        return self._report(self._lib.raft_audit_report_dev, g0, n, out_ptr, max_events, "raft_audit_report_dev")
+
+    def read(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """The ledgers of groups [g0, g0 + n): [n, 8 + 2 R] int32 (abi.AUDIT_WORDS,
+        then (currentTerm, votedFor) per replica)."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(int(n), 0), self.words), dtype=np.int32)   # a bad range is the library's to refuse
+        self._check(self._lib.raft_audit_read(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "raft_audit_read")
+        return out
+
+    def write(self, ledger: np.ndarray, g0: int = 0):
+        """Store the ledgers of groups [g0, g0 + len(ledger)) (resuming an
+        audit): an integer [n, 8 + 2 R] array.  The library refuses unknown flag
+        bits, a lead_replica outside -1..R-1 and an anchor_count outside
+        0..log_cap, and stores nothing then."""
+        a = np.asarray(ledger)
+        if a.ndim != 2 or a.shape[1] != self.words or a.dtype.kind not in "iu":
+            raise ValueError(f"audit write: ledger {a.shape} {a.dtype} must be an integer array of shape "
+                             f"(n, {self.words})")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        self._check(self._lib.raft_audit_write(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "raft_audit_write")
+
+
 class RaftEngine:
     def __init__(self, params: abi.raft_params, device: int = 0):
         self._lib = abi.load_library()
@@ -82,6 +204,10 @@ class RaftEngine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ref in getattr(self, "_audits", ()):                  # an audit goes before its engine
+                a = ref()
+                if a is not None:
+                    a.close()
             self._lib.raft_engine_destroy(self._h)
             self._h = None
 
@@ -885,6 +1011,17 @@ class RaftEngine:
             raise ValueError(f"write_watch: every pair must be (-1, 0) or (leader in 0..{self.R - 1}, term >= 0)")
         a = np.ascontiguousarray(a, dtype=np.int32)
         self._check(self._lib.raft_engine_write_watch(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "write_watch")
+
+    # -- the safety audit (raft_audit_*) ----------------------------------------------------------------
+    def audit(self) -> RaftAudit:
+        """A new safety audit of this engine, every ledger in its zero state
+        (RaftAudit: observe, report, read, write, reset, close).  Closing the
+        engine closes its audits first."""
+        a = RaftAudit(self)
+        if not hasattr(self, "_audits"):
+            self._audits = []
+        self._audits.append(weakref.ref(a))
+        return a
 
     # -- the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*) ---------------------------------
     def outbox_configure(self, capacity: int, expire_steps: int = 0):

@@ -34,6 +34,9 @@ argument meaning and error behaviour:
 * ``RaftService.submit_reliable`` / ``completions`` / ``pump_until_idle``: the
   engine's proposal outbox -- commands held on the device until committed,
   re-proposed only when no replica holds them any more, completed once
+* ``RaftService.check_safety`` / ``violations``: the engine's safety audit --
+  Raft's invariants checked over time on the device, and the groups that
+  broke one, with the step at which it was first seen
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -445,6 +448,29 @@ class RaftService:
             raise IndexError(group)
         r = int(self.leader_of[group]) if hasattr(self, "leader_of") else -1
         return None if r < 0 else RaftNode(self, group, r)
+
+    # -- the safety audit: did safety hold, and if not, in which groups and since when ------------------
+    def check_safety(self, g0: int = 0, n: Optional[int] = None) -> dict:
+        """Observe groups [g0, g0 + n) with this service's safety audit
+        (RaftEngine.audit, made at the first call): the state now against what
+        the audit remembers of earlier calls.  Returns the observe's info --
+        newly_flagged, flagged, one count per kind (abi.AUDIT_KINDS), unknown;
+        ``last_safety`` keeps it.  flagged == 0 in textbook mode without
+        amnesia restarts; otherwise `violations` says where and since when.
+        After RaftEngine.reset call ``safety_audit.reset()`` too."""
+        if getattr(self, "safety_audit", None) is None:
+            self.safety_audit = self.engine.audit()
+        self.last_safety = self.safety_audit.observe(g0, n)
+        return self.last_safety
+
+    def violations(self, max_events: Optional[int] = None) -> np.ndarray:
+        """The groups check_safety has flagged so far (abi.AUDIT_EVENT_DTYPE:
+        group, flags of abi.AUDIT_*, first_step), in ascending group order, at
+        most max_events of them.  Nothing is consumed; empty before the first
+        check_safety."""
+        if getattr(self, "safety_audit", None) is None:
+            return np.zeros(0, dtype=abi.AUDIT_EVENT_DTYPE)
+        return self.safety_audit.report(max_events=max_events)[1]
 
     def submit(self, groups, commands: List[str]) -> np.ndarray:
         """One command per entry of `groups`, routed to each group's leader in
