@@ -18,14 +18,14 @@
 //              the wave's offsets (shuffles), reads that 8-byte log slot
 //              (lanes inside one run read consecutive slots) and the 24-byte
 //              records leave through LDS as contiguous 512-byte stores
+// The scan scratch, the record buffer and the publish through LDS are
+// raft_stream.h's, shared with the other record streams.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -72,10 +72,6 @@ __global__ __launch_bounds__(BLOCK) void apply_count_kernel(DevParams p, int32_t
         if (wr) atomicAdd(hdr + HDR_REGRESSED, (unsigned long long)wr);
     }
 }
-
-struct CountToOffset {
-    __host__ __device__ unsigned long long operator()(uint32_t c) const { return c; }
-};
 
 // pass 3.  Wave w of the grid owns replicas [64 w, 64 w + 64) of the selection
 // and their output slots [off[64 w], off[64 w + 64)), cut at max_entries.
@@ -135,20 +131,8 @@ __global__ __launch_bounds__(BLOCK) void apply_expand_kernel(DevParams p, int32_
             st[3 * lane + 1] = make_uint2((uint32_t)orr, (uint32_t)index);
             st[3 * lane + 2] = e;                                      // (term, cmd) as the log holds them
         }
-        // the wave's own LDS accesses complete in order: only the compiler must keep them so
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t words = 3 * min(64u, end - x0);
-        uint2* o = out + (base + x0) * 3;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const uint32_t wd = q * 64 + lane;
-            if (wd < words) o[wd] = st[wd];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_publish<3>(st, out + (base + x0) * 3, 3 * min(64u, end - x0));
+        wave_lds_fence();                                              // the next trip stages into st again
     }
     // lastApplied moves past what was written, once per replica
     if (mine && my_cnt) {
@@ -185,38 +169,27 @@ int drain(raft_engine* e, int64_t g0, int64_t n, int32_t replica, raft_applied_e
     if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
     if (int rc = check_groups(e, g0, n)) return rc;
     if (replica < -1 || replica >= e->p.R) return raft_internal_fail(RAFT_EINVAL, "replica must be -1 or in 0..R-1");
-    if (max_entries < 0) return raft_internal_fail(RAFT_EINVAL, "max_entries must be >= 0");
-    if (!out && max_entries > 0) return raft_internal_fail(RAFT_EINVAL, "null record buffer with max_entries > 0");
+    if (int rc = check_records(out, max_entries, out_on_host, 0, "max_entries")) return rc;
     *info = raft_drain_info{0, 0, 0, 0};
     if (n == 0) return RAFT_OK;
     const bool peek = !out && max_entries == 0;
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;                           // later step launches wait for these reads of the state and logs
     const Sel s{g0, replica < 0 ? n * e->p.R : n, replica};
-    const size_t items = (size_t)s.N + 1;
-    const auto counts_of = [](uint32_t* c) { return rocprim::make_transform_iterator(c, CountToOffset{}); };
-    size_t scan_b = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, counts_of(nullptr), (unsigned long long*)nullptr, 0ull, items,
-                                    rocprim::plus<unsigned long long>(), e->stream));
-    const size_t cnt_b = al256(items * 4), off_b = al256(items * 8);
-    if (int rc = raft_internal_grow_dev(e, &e->apl, &e->apl_bytes, HDR_BYTES + cnt_b + off_b + al256(scan_b))) return rc;
-    unsigned long long* hdr = (unsigned long long*)e->apl;
-    uint32_t* cnt = (uint32_t*)(e->apl + HDR_BYTES);
-    unsigned long long* off = (unsigned long long*)(e->apl + HDR_BYTES + cnt_b);
-    void* scan_tmp = e->apl + HDR_BYTES + cnt_b + off_b;
+    ScanScratch<uint32_t> sc;                        // one item per selected replica and the zero behind them
+    if (int rc = sc.init(e, &e->apl, &e->apl_bytes, HDR_BYTES, (size_t)s.N + 1)) return rc;
+    unsigned long long* hdr = (unsigned long long*)sc.head;
 
     if (int rc = mark(e, 0)) return rc;
     HIP_TRY(hipMemsetAsync(hdr, 0, HDR_BYTES, e->stream));
-    by_R<CountL>(e->p.R, e, s, peek ? 1 : 0, cnt, hdr);
+    by_R<CountL>(e->p.R, e, s, peek ? 1 : 0, sc.cnt, hdr);
     HIP_TRY(hipGetLastError());
     if (int rc = mark(e, 1)) return rc;
-    HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_b, counts_of(cnt), off, 0ull, items,
-                                    rocprim::plus<unsigned long long>(), e->stream));
-    HIP_TRY(hipGetLastError());
+    if (int rc = sc.run(e)) return rc;
     if (int rc = mark(e, 2)) return rc;
     unsigned long long h[2] = {0, 0}, total = 0;
     HIP_TRY(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(&total, off + s.N, 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(&total, sc.off + s.N, 8, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const int64_t delivered = peek ? 0 : std::min<int64_t>((int64_t)total, max_entries);
     info->delivered = delivered;
@@ -224,21 +197,14 @@ int drain(raft_engine* e, int64_t g0, int64_t n, int32_t replica, raft_applied_e
     info->lost = (int64_t)h[HDR_LOST];
     info->regressed = (int64_t)h[HDR_REGRESSED];
     if (delivered > 0) {
-        uint2* dst = (uint2*)out;
-        if (out_on_host) {
-            if (int rc = raft_internal_grow_dev(e, &e->apo, &e->apo_bytes, (size_t)delivered * sizeof(raft_applied_entry)))
-                return rc;
-            dst = (uint2*)e->apo;
-        }
+        Records rec;
+        if (int rc = rec.begin(e, out, (size_t)delivered * sizeof(raft_applied_entry), out_on_host)) return rc;
         if (int rc = mark(e, 3)) return rc;
-        by_R<ExpandL>(e->p.R, e, s, cnt, off, dst, max_entries);
+        by_R<ExpandL>(e->p.R, e, s, sc.cnt, sc.off, (uint2*)rec.dev, max_entries);
         HIP_TRY(hipGetLastError());
         if (int rc = mark(e, 4)) return rc;
-        if (out_on_host)
-            HIP_TRY(hipMemcpyAsync(out, dst, (size_t)delivered * sizeof(raft_applied_entry), hipMemcpyDeviceToHost,
-                                   e->stream));
+        if (int rc = rec.finish(e)) return rc;
     }
-    if (delivered > 0) HIP_TRY(hipStreamSynchronize(e->stream));
     e->drain_expanded = delivered > 0;
     if (info->lost > 0)
         return raft_internal_fail(RAFT_EWINDOW, std::to_string(info->lost) +

@@ -18,25 +18,20 @@
 //             the group's byte of a ballot; lane 0 stores the header.  The
 //             counts of a call go through ballots into a stripe (one atomic per
 //             nonzero word and wave).
-//   report    the watch's three passes with the predicate flags != 0: flag
-//             (per-wave counts), an exclusive scan of them (rocprim), a staged
-//             contiguous write of 16-byte records.  The order of the records
-//             comes from the scan, never from an atomic.  Passes 2 and 3 run
-//             only when something is delivered.
+//   report    the stream of raft_stream.h, as the leader
+//             watch's, over the source "flags != 0": 16-byte records in group
+//             order.  Its scan and write run only when something is delivered.
 // The ledger on the device: hdr, two int4 per group (flags, first_step,
 // lead_term, lead_replica | anchor_count, anchor_term, anchor_cmd,
 // anchor_seen_term), and pairs, one int2 (currentTerm, votedFor) per replica at
 // g * R + r -- a wave's 32 groups read one contiguous run of each.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
-#include <algorithm>
 #include <climits>
 #include <string>
 #include <vector>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -189,69 +184,42 @@ __global__ __launch_bounds__(BLOCK) void audit_observe_kernel(DevParams p, int4*
                              b_l = __ballot(got & RAFT_AUDIT_LEADER_INCOMPLETE);
     const uint32_t unk = (uint32_t)(__popcll(__ballot(unk_a)) + __popcll(__ballot(unk_b)) + __popcll(__ballot(unk_n)));
     if ((threadIdx.x & 63) == 0) {
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-        unsigned long long* line = cnt + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
-        if (b_new) atomicAdd(line + AW_NEWLY, (unsigned long long)__popcll(b_new));
-        if (b_fl) atomicAdd(line + AW_FLAGGED, (unsigned long long)__popcll(b_fl));
-        if (b_t) atomicAdd(line + AW_TERM, (unsigned long long)__popcll(b_t));
-        if (b_v) atomicAdd(line + AW_VOTE, (unsigned long long)__popcll(b_v));
-        if (b_2) atomicAdd(line + AW_TWO, (unsigned long long)__popcll(b_2));
-        if (b_c) atomicAdd(line + AW_COMMIT, (unsigned long long)__popcll(b_c));
-        if (b_l) atomicAdd(line + AW_LEADER, (unsigned long long)__popcll(b_l));
-        if (unk) atomicAdd(line + AW_UNKNOWN, (unsigned long long)unk);
+        unsigned long long* line = stripe_of(cnt, wave_index());
+        tally_ballot(line, AW_NEWLY, b_new);
+        tally_ballot(line, AW_FLAGGED, b_fl);
+        tally_ballot(line, AW_TERM, b_t);
+        tally_ballot(line, AW_VOTE, b_v);
+        tally_ballot(line, AW_TWO, b_2);
+        tally_ballot(line, AW_COMMIT, b_c);
+        tally_ballot(line, AW_LEADER, b_l);
+        tally(line, AW_UNKNOWN, unk);
     }
 }
 
-// report, pass 1.  wcnt[w]: flagged groups among groups [64 w, 64 w + 64) of the range
-__global__ __launch_bounds__(BLOCK) void audit_flag_kernel(const int4* __restrict__ hdr, int64_t g0, int64_t n,
-                                                           uint32_t* __restrict__ wcnt, unsigned long long* cnt) {
-    const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const bool live = j < n;
-    const int64_t g = g0 + (live ? j : n - 1);
-    const unsigned long long b = __ballot(live && hdr[2 * g].x != 0);
-    if ((threadIdx.x & 63) == 0 && live) {                              // lane 0 live: the wave is inside the range
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-        wcnt[wave] = (uint32_t)__popcll(b);
-        if (b) atomicAdd(cnt + (wave & (HDR_STRIPES - 1)) * HDR_LINE, (unsigned long long)__popcll(b));
-    }
-}
+// the report's source (raft_stream.h): a group's first header quad, a record iff its flags are set
+struct AuditSource {
+    using Word = uint4;
+    static constexpr int WORDS = 1, TALLIES = 1;                        // word 0 (AW_NEWLY's place): the flagged groups
+    struct Item {
+        int4 H0;
+        bool hit;
+    };
+    const int4* __restrict__ hdr;
 
-struct CountToOffset {
-    __host__ __device__ unsigned long long operator()(uint32_t c) const { return c; }
+    __device__ __forceinline__ Item eval(int64_t g, bool live) const {
+        const int4 H0 = hdr[2 * g];
+        return Item{H0, live && H0.x != 0};
+    }
+    __device__ __forceinline__ void tallies(const Item& it, bool, unsigned long long (&b)[TALLIES]) const {
+        b[0] = __ballot(it.hit);
+    }
+    __device__ __forceinline__ void record(const Item& it, int64_t g, uint4* st) const {
+        st[0] = make_uint4((uint32_t)((uint64_t)g & 0xFFFFFFFFu), (uint32_t)((uint64_t)g >> 32), (uint32_t)it.H0.x,
+                           (uint32_t)it.H0.y);
+    }
+    __device__ __forceinline__ void commit(const Item&, int64_t) const {}   // a report changes nothing
+    static int64_t total(const unsigned long long* w) { return (int64_t)w[0]; }
 };
-
-// report, pass 3.  Wave w owns groups [64 w, 64 w + 64) of the range and the
-// output slots [off[w], off[w] + wcnt[w]), cut at max_events.
-__global__ __launch_bounds__(BLOCK) void audit_write_kernel(const int4* __restrict__ hdr, int64_t g0, int64_t n,
-                                                            const uint32_t* __restrict__ wcnt,
-                                                            const unsigned long long* __restrict__ off,
-                                                            uint4* __restrict__ out, int64_t max_events) {
-    __shared__ uint4 stage[WAVES_PER_BLOCK][64];                       // 64 records of 16 bytes per wave
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
-    const int64_t j0 = wave * 64;
-    if (j0 >= n) return;                                               // wave-uniform
-    const uint32_t c = wcnt[wave];
-    const unsigned long long base = off[wave], room = (unsigned long long)max_events;
-    if (c == 0 || base >= room) return;                                // wave-uniform: nothing of this wave is written
-    const uint32_t take = (uint32_t)min((unsigned long long)c, room - base);
-    const int64_t j = j0 + lane;
-    const bool live = j < n;
-    const int64_t g = g0 + (live ? j : n - 1);
-    const int4 H0 = hdr[2 * g];
-    const bool f = live && H0.x != 0;
-    // the ledger is the flag pass's: the ballot has c bits, so every rank is below 64
-    const uint32_t rank = (uint32_t)__popcll(__ballot(f) & ((1ull << lane) - 1ull));
-    uint4* st = stage[wv];
-    if (f && rank < take)
-        st[rank] = make_uint4((uint32_t)((uint64_t)g & 0xFFFFFFFFu), (uint32_t)((uint64_t)g >> 32), (uint32_t)H0.x,
-                              (uint32_t)H0.y);
-    // the wave's own LDS accesses complete in order: only the compiler must keep them so
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if ((uint32_t)lane < take) out[base + lane] = st[lane];            // base + take <= max_events: inside out
-}
 
 int check_audit(raft_audit* a, int64_t g0, int64_t n) {
     if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
@@ -274,50 +242,15 @@ int report(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out, int64_t 
     *info = raft_audit_report_info{};
     raft_engine* e = a->e;
     if (int rc = check_groups(e, g0, n)) return rc;
-    if (max_events < 0) return raft_internal_fail(RAFT_EINVAL, "max_events must be >= 0");
-    if (!out && max_events > 0) return raft_internal_fail(RAFT_EINVAL, "null record buffer with max_events > 0");
-    if (!out_on_host && !aligned16(out)) return raft_internal_fail(RAFT_EINVAL, "the record buffer must be 16-byte aligned");
+    if (int rc = check_records(out, max_events, out_on_host, 16, "max_events")) return rc;
     if (n == 0) return RAFT_OK;
     HIP_TRY(hipSetDevice(e->device));
     e->fork_needed = true;
-    const size_t nwaves = (size_t)((n + 63) / 64);
-    const auto counts_of = [](uint32_t* c) { return rocprim::make_transform_iterator(c, CountToOffset{}); };
-    size_t scan_b = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, counts_of(nullptr), (unsigned long long*)nullptr, 0ull, nwaves,
-                                    rocprim::plus<unsigned long long>(), e->stream));
-    const size_t cnt_b = al256(nwaves * 4), off_b = al256(nwaves * 8);
-    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Counts::BYTES + cnt_b + off_b + al256(scan_b)))
-        return rc;
-    uint32_t* wcnt = (uint32_t*)(e->aux + Counts::BYTES);
-    unsigned long long* off = (unsigned long long*)(e->aux + Counts::BYTES + cnt_b);
-    void* scan_tmp = e->aux + Counts::BYTES + cnt_b + off_b;
-    Counts c;
-    if (int rc = c.zero(e, e->aux)) return rc;
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
-    audit_flag_kernel<<<grid, BLOCK, 0, e->stream>>>(a->hdr, g0, n, wcnt, c.dev);
-    HIP_TRY(hipGetLastError());
-    if (int rc = c.fetch(e)) return rc;
-    const int64_t total = (int64_t)c.w[0];
-    const int64_t delivered = out ? std::min(total, max_events) : 0;
-    info->delivered = delivered;
-    info->pending = total - delivered;
-    info->flagged = total;
-    if (delivered == 0) return RAFT_OK;
-    uint4* dst = (uint4*)out;
-    if (out_on_host) {
-        if (int rc = raft_internal_grow_dev(e, &e->apo, &e->apo_bytes, (size_t)delivered * sizeof(raft_audit_event)))
-            return rc;
-        dst = (uint4*)e->apo;
-    }
-    HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_b, counts_of(wcnt), off, 0ull, nwaves,
-                                    rocprim::plus<unsigned long long>(), e->stream));
-    HIP_TRY(hipGetLastError());
-    audit_write_kernel<<<grid, BLOCK, 0, e->stream>>>(a->hdr, g0, n, wcnt, off, dst, max_events);
-    HIP_TRY(hipGetLastError());
-    if (out_on_host)
-        HIP_TRY(hipMemcpyAsync(out, dst, (size_t)delivered * sizeof(raft_audit_event), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    StreamTotals<AuditSource> c{};
+    const int rc = stream_records(e, AuditSource{a->hdr}, g0, n, out, max_events, out_on_host, c, &info->delivered);
+    info->flagged = AuditSource::total(c.w);
+    info->pending = info->flagged - info->delivered;
+    return rc;
 }
 
 }  // namespace

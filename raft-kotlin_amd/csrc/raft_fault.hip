@@ -35,7 +35,7 @@
 
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -148,10 +148,10 @@ __global__ __launch_bounds__(BLOCK) void restart_kernel(DevParams p, RestartArgs
     const uint64_t lead = __ballot(was_leader);
     const uint32_t wd = wave_sum(dropped);                              // 64 lastIndex values of < 2^23 each
     if (lane == 0) {
-        unsigned long long* line = a.hdr + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
-        atomicAdd(line + HDR_RESTARTED, (unsigned long long)__popcll(bal));
-        if (lead) atomicAdd(line + HDR_LEADERS, (unsigned long long)__popcll(lead));
-        if (wd) atomicAdd(line + HDR_DROPPED, (unsigned long long)wd);
+        unsigned long long* line = stripe_of(a.hdr, wave);
+        atomicAdd(line + HDR_RESTARTED, (unsigned long long)__popcll(bal));   // (bal != 0: the wave selected something)
+        tally_ballot(line, HDR_LEADERS, lead);
+        tally(line, HDR_DROPPED, wd);
     }
 }
 

@@ -19,7 +19,7 @@
 #include <cstring>
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -79,14 +79,13 @@ __global__ __launch_bounds__(BLOCK) void noop_kernel(DevParams p, int64_t g0, in
                              b_app = __ballot(live && (tk.w == RAFT_PROPOSE_ACCEPTED || tk.w == RAFT_PROPOSE_GHOSTED)),
                              b_miss = __ballot(miss);
     if ((threadIdx.x & 63) == 0) {
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-        unsigned long long* line = hdr + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
-        if (b_app) atomicAdd(line + NW_APPENDED, (unsigned long long)__popcll(b_app));
-        if (b_cur) atomicAdd(line + NW_CURRENT, (unsigned long long)__popcll(b_cur));
-        if (b_nol) atomicAdd(line + NW_NO_LEADER, (unsigned long long)__popcll(b_nol));
-        if (b_full) atomicAdd(line + NW_LOG_FULL, (unsigned long long)__popcll(b_full));
-        if (b_gho) atomicAdd(line + NW_GHOSTED, (unsigned long long)__popcll(b_gho));
-        if (b_miss) atomicAdd(line + NW_MISS, (unsigned long long)__popcll(b_miss));
+        unsigned long long* line = stripe_of(hdr, wave_index());
+        tally_ballot(line, NW_APPENDED, b_app);
+        tally_ballot(line, NW_CURRENT, b_cur);
+        tally_ballot(line, NW_NO_LEADER, b_nol);
+        tally_ballot(line, NW_LOG_FULL, b_full);
+        tally_ballot(line, NW_GHOSTED, b_gho);
+        tally_ballot(line, NW_MISS, b_miss);
     }
 }
 

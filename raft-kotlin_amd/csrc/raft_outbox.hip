@@ -51,14 +51,13 @@
 //   5. scatter   one thread per retried record: its new ticket into the
 //                survivor, tries + 1, the outcome counts per wave
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <climits>
 #include <cstddef>
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 #include "raft_ticket.h"
 
 using namespace raft;
@@ -168,11 +167,9 @@ __global__ __launch_bounds__(BLOCK) void outbox_verdict_kernel(DevParams p, cons
     for (int k = 0; k < V_KINDS; ++k) cnt[k] = (uint32_t)__popcll(__ballot(lead && code == k));
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) {
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
-        unsigned long long* line = tot + (wave & (HDR_STRIPES - 1)) * TOT_LINE;
+        unsigned long long* line = stripe_of(tot, wave_index(), TOT_LINE);
 #pragma unroll
-        for (int k = 0; k < V_KINDS; ++k)
-            if (cnt[k]) atomicAdd(line + k, (unsigned long long)cnt[k]);
+        for (int k = 0; k < V_KINDS; ++k) tally(line, k, cnt[k]);
         wc[wv] = ((unsigned long long)(cnt[V_COMMITTED] + cnt[V_EXPIRED]) << 32) | cnt[V_RETRY];
     }
     __syncthreads();
@@ -255,11 +252,9 @@ __global__ __launch_bounds__(BLOCK) void outbox_scatter_kernel(int4* __restrict_
     const uint64_t b[4] = {__ballot(st == RAFT_PROPOSE_ACCEPTED), __ballot(st == RAFT_PROPOSE_GHOSTED),
                            __ballot(st == RAFT_PROPOSE_NO_LEADER), __ballot(st == RAFT_PROPOSE_LOG_FULL)};
     if ((threadIdx.x & 63) == 0) {
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-        unsigned long long* line = tot + (wave & (HDR_STRIPES - 1)) * TOT_LINE;
+        unsigned long long* line = stripe_of(tot, wave_index(), TOT_LINE);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (b[k]) atomicAdd(line + T_ACCEPTED + k, (unsigned long long)__popcll(b[k]));
+        for (int k = 0; k < 4; ++k) tally_ballot(line, T_ACCEPTED + k, b[k]);
     }
 }
 
@@ -312,31 +307,23 @@ int pump(raft_engine* e, raft_outbox_done* done, int64_t max_done, int64_t* n_do
     if (!n_done || !info) return raft_internal_fail(RAFT_EINVAL, "null n_done or info");
     *n_done = 0;
     *info = raft_outbox_info{};
-    if (max_done < 0) return raft_internal_fail(RAFT_EINVAL, "max_done must be >= 0");
-    if (!done && max_done > 0) return raft_internal_fail(RAFT_EINVAL, "null record buffer with max_done > 0");
-    if (!on_host && !aligned16(done)) return raft_internal_fail(RAFT_EINVAL, "the record buffer must be 16-byte aligned");
+    if (int rc = check_records(done, max_done, on_host, 16, "max_done")) return rc;
     Ob ob;
     if (int rc = ob_load(e, ob)) return rc;
     const int64_t n = ob.len;
     if (n == 0) return RAFT_OK;
     e->fork_needed = true;                           // later step launches wait for these reads of the state and logs
     const size_t ntile = (size_t)((n + TILE_RECS - 1) / TILE_RECS);
-    size_t scan_b = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull,
-                                    ntile, rocprim::plus<unsigned long long>(), e->stream));
-    const size_t v_b = al256((size_t)n), c_b = al256(ntile * 8);
-    if (int rc = raft_internal_grow_dev(e, &e->apl, &e->apl_bytes, OBS_HEAD + v_b + 2 * c_b + al256(scan_b))) return rc;
-    uint8_t* verdict = (uint8_t*)(e->apl + OBS_HEAD);
-    unsigned long long* tcnt = (unsigned long long*)(e->apl + OBS_HEAD + v_b);
-    unsigned long long* off = (unsigned long long*)(e->apl + OBS_HEAD + v_b + c_b);
-    void* scan_tmp = e->apl + OBS_HEAD + v_b + 2 * c_b;
+    ScanScratch<unsigned long long> sc;              // the packed (done, retry) counts; the verdicts end the head
+    if (int rc = sc.init(e, &e->apl, &e->apl_bytes, OBS_HEAD + al256((size_t)n), ntile)) return rc;
+    uint8_t* verdict = (uint8_t*)(sc.head + OBS_HEAD);
     Tot tot;
     Hist hist;
-    if (int rc = tot.zero(e, e->apl + OBS_TOT)) return rc;
-    if (int rc = hist.zero(e, e->apl + OBS_HIST)) return rc;
+    if (int rc = tot.zero(e, sc.head + OBS_TOT)) return rc;
+    if (int rc = hist.zero(e, sc.head + OBS_HIST)) return rc;
     const int4* q = half_of(e, ob.half);
     const int64_t now = (int64_t)e->t;
-    outbox_verdict_kernel<<<(unsigned)ntile, BLOCK, 0, e->stream>>>(e->dp, q, n, now, (int32_t)ob.expire, verdict, tcnt, tot.dev);
+    outbox_verdict_kernel<<<(unsigned)ntile, BLOCK, 0, e->stream>>>(e->dp, q, n, now, (int32_t)ob.expire, verdict, sc.cnt, tot.dev);
     HIP_TRY(hipGetLastError());
     if (int rc = tot.fetch(e)) return rc;            // the read-back inside a pump: what is done, what retries
     const int64_t n_fin = (int64_t)(tot.w[V_COMMITTED] + tot.w[V_EXPIRED]), n_retry = (int64_t)tot.w[V_RETRY];
@@ -350,12 +337,8 @@ int pump(raft_engine* e, raft_outbox_done* done, int64_t max_done, int64_t* n_do
     info->left = n - emitted;
     int prc = RAFT_OK;
     if (emitted > 0 || n_retry > 0) {
-        int4* dst = (int4*)done;
-        if (on_host && emitted > 0) {
-            if (int rc = raft_internal_grow_dev(e, &e->apo, &e->apo_bytes, (size_t)emitted * sizeof(raft_outbox_done)))
-                return rc;
-            dst = (int4*)e->apo;
-        }
+        Records rec;                                                   // (nothing emitted: nothing staged or copied back)
+        if (int rc = rec.begin(e, done, (size_t)emitted * sizeof(raft_outbox_done), on_host)) return rc;
         // the gathered retries, in the client path's staging: groups, commands, positions, the new tickets
         const size_t g_b = al256((size_t)n_retry * 8), u_b = al256((size_t)n_retry * 4), t_b = al256((size_t)n_retry * 16);
         if (n_retry > 0)
@@ -365,11 +348,10 @@ int pump(raft_engine* e, raft_outbox_done* done, int64_t max_done, int64_t* n_do
         uint32_t* rc_ = (uint32_t*)(rb + g_b);
         uint32_t* rpos = (uint32_t*)(rb + g_b + u_b);
         raft_ticket* rtk = (raft_ticket*)(rb + g_b + 2 * u_b);
-        HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_b, tcnt, off, 0ull, ntile, rocprim::plus<unsigned long long>(),
-                                        e->stream));
+        if (int rc = sc.run(e)) return rc;
         int4* q_out = half_of(e, ob.half ^ 1);
         outbox_split_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
-            q, q_out, verdict, off, n, max_done, now, dst, rg, rc_, rpos, hist.dev);
+            q, q_out, verdict, sc.off, n, max_done, now, (int4*)rec.dev, rg, rc_, rpos, hist.dev);
         HIP_TRY(hipGetLastError());
         if (n_retry > 0) {
             if (int rc = raft_internal_propose_enqueue(e, rg, rc_, rtk, (int)n_retry)) return rc;
@@ -377,13 +359,11 @@ int pump(raft_engine* e, raft_outbox_done* done, int64_t max_done, int64_t* n_do
                 q_out, rpos, (const int4*)rtk, n_retry, tot.dev);
             HIP_TRY(hipGetLastError());
         }
-        if (on_host && emitted > 0)
-            HIP_TRY(hipMemcpyAsync(done, dst, (size_t)emitted * sizeof(raft_outbox_done), hipMemcpyDeviceToHost, e->stream));
         // from here on the other half is the queue, whatever the propose reports
         ob.half ^= 1;
         ob.len = n - emitted;
         HIP_TRY(hipMemcpyAsync(ob_hdr(e), &ob, sizeof(Ob), hipMemcpyHostToDevice, e->stream));   // (waited for below)
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (int rc = rec.finish(e)) return rc;
         if (n_retry > 0) {
             prc = raft_internal_propose_finish(e);
             if (prc != RAFT_OK && prc != RAFT_EWINDOW) return prc;

@@ -32,7 +32,7 @@
 
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -53,13 +53,6 @@ __device__ __forceinline__ uint64_t sm_x(int32_t i, uint32_t t, uint32_t c) {
     z ^= z >> 27; z *= 0x94D049BB133111EBull;
     z ^= z >> 31;
     return z;
-}
-
-// the wave's own LDS accesses complete in order: only the compiler must keep them so
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // One entry of a 64-entry batch, as its lane holds it: the owner lane k, the
@@ -122,10 +115,10 @@ __global__ __launch_bounds__(BLOCK) void sm_apply_kernel(DevParams p, Sel s, int
     // the totals: one atomic per wave and word, into the wave's stripe of the header
     const uint32_t ws = wave_sum(skip), wr = wave_sum(regressed);
     if (lane == 0) {
-        unsigned long long* line = hdr + ((j0 >> 6) & (HDR_STRIPES - 1)) * HDR_LINE;
-        if (span) atomicAdd(line + HDR_APPLIED, (unsigned long long)span);
-        if (ws) atomicAdd(line + HDR_LOST, (unsigned long long)ws);
-        if (wr) atomicAdd(line + HDR_REGRESSED, (unsigned long long)wr);
+        unsigned long long* line = stripe_of(hdr, j0 >> 6);              // the wave's tile of the selection
+        tally(line, HDR_APPLIED, span);
+        tally(line, HDR_LOST, ws);
+        tally(line, HDR_REGRESSED, wr);
     }
     uint64_t hash = (uint64_t)(uint32_t)hd.z | (uint64_t)(uint32_t)hd.w << 32;
     if (span) {                                                        // wave-uniform

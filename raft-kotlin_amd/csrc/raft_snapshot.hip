@@ -37,7 +37,7 @@
 
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -102,12 +102,12 @@ __global__ __launch_bounds__(BLOCK) void install_kernel(DevParams p, InstallArgs
     // ---- the totals but the slots; a wave that installs nothing is done
     const uint64_t b_nl = __ballot(live && r == 0 && L < 0), b_gp = __ballot(live && r == 0 && L >= 0 && gapped);
     const uint64_t b_ah = __ballot(ahead);
-    unsigned long long* line = a.hdr + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
+    unsigned long long* line = stripe_of(a.hdr, wave);
     if (lane == 0) {
-        if (bal) atomicAdd(line + HDR_INSTALLED, (unsigned long long)__popcll(bal));
-        if (b_nl) atomicAdd(line + HDR_NO_LEADER, (unsigned long long)__popcll(b_nl));
-        if (b_gp) atomicAdd(line + HDR_GAPPED, (unsigned long long)__popcll(b_gp));
-        if (b_ah) atomicAdd(line + HDR_AHEAD, (unsigned long long)__popcll(b_ah));
+        tally_ballot(line, HDR_INSTALLED, bal);
+        tally_ballot(line, HDR_NO_LEADER, b_nl);
+        tally_ballot(line, HDR_GAPPED, b_gp);
+        tally_ballot(line, HDR_AHEAD, b_ah);
     }
     if (bal == 0) return;                                               // wave-uniform
     // this lane's group: which of its replicas are installed (0 on a dead lane)

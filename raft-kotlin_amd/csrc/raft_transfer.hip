@@ -25,7 +25,7 @@
 
 #include <string>
 
-#include "raft_engine_impl.h"
+#include "raft_stream.h"
 
 using namespace raft;
 
@@ -252,14 +252,13 @@ __global__ __launch_bounds__(BLOCK) void evacuate_kernel(DevParams p, int64_t g0
     const unsigned long long b_led = __ballot(led), b_sent = __ballot(sent), b_behind = __ballot(behind),
                              b_busy = __ballot(busy);
     if ((threadIdx.x & 63) == 0 && b_led) {
-        const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-        unsigned long long* line = hdr + (wave & (HDR_STRIPES - 1)) * HDR_LINE;
+        unsigned long long* line = stripe_of(hdr, wave_index());
         const unsigned long long n_led = __popcll(b_led), n_sent = __popcll(b_sent);
-        atomicAdd(line + EV_LED, n_led);
-        if (b_sent) atomicAdd(line + EV_SENT, n_sent);
-        if (n_led != n_sent) atomicAdd(line + EV_NO_TARGET, n_led - n_sent);
-        if (b_behind) atomicAdd(line + EV_BEHIND, (unsigned long long)__popcll(b_behind));
-        if (b_busy) atomicAdd(line + EV_BUSY, (unsigned long long)__popcll(b_busy));
+        atomicAdd(line + EV_LED, n_led);                                // (b_led != 0)
+        tally(line, EV_SENT, n_sent);
+        tally(line, EV_NO_TARGET, n_led - n_sent);
+        tally_ballot(line, EV_BEHIND, b_behind);
+        tally_ballot(line, EV_BUSY, b_busy);
     }
 }
 

@@ -10,7 +10,7 @@ import pytest
 
 import restart_model as RM
 import watch_model as WM
-from helpers import abi, assert_same_state, high_g0
+from helpers import abi, assert_same_state, blank_groups, high_g0, set_fld
 
 pytestmark = pytest.mark.gpu
 
@@ -127,6 +127,64 @@ def test_the_cut(R, G):
             for info in infos:                                      # the counts describe the range at each call
                 assert sum(info[k] for k in WM.KINDS) == info["delivered"] + info["pending"]
                 assert info["leaderless"] == whole_info["leaderless"]
+
+
+def test_past_one_workgroup_and_a_partial_last_wave():
+    """G = 70,001, R = 3 (the audit's test of this name, for the other user of
+    the shared stream kernels): a state built in numpy and loaded with
+    write_state, never stepped.  Groups [0, 640) all have a leader (waves of 64
+    hits: rank 63), [640, 1280) none (waves with no hit), from 1280 on every
+    7th.  [3, G - 2) polled with room for everything, in two parts cut at half,
+    and in the _dev form: events, info and read_watch are the model's."""
+    import torch
+    R, G = 3, 70_001
+    g0, n = 3, G - 5
+    g = np.arange(G)
+    led = (g < 640) | ((g >= 1280) & ((g - 1280) % 7 == 0))
+    w = blank_groups(G, R)
+    for r in range(R):
+        mine = led & (g % R == r)
+        rows = w[mine]                                              # (a boolean index copies: stored back below)
+        set_fld(rows, R, r, "role", abi.LEADER)
+        set_fld(rows, R, r, "term", 1 + g[mine] % 5)
+        w[mine] = rows
+    # by arithmetic: 637 groups of [3, 640), and 1280 + 7 k < G - 2 for k = 0 .. 9816
+    total = 637 + 9817
+    assert total == 10_454 == int(led[g0:g0 + n].sum())
+    cur = WM.current(w, R)
+    want_info, want_ev, rc = WM.poll(w, WM.fresh(G), R, g0, n, cur=cur)
+    assert rc == abi.RAFT_OK and len(want_ev) == total
+    assert want_info == dict(delivered=total, pending=0, gained=total, lost=0, moved=0, reterm=0, leaderless=n - total)
+    with RaftEngine(abi.make_params(R=R, G=G, log_cap=16)) as e:
+        e.write_state(w)
+        # once, with room for everything
+        seen = WM.fresh(G)
+        assert WM.poll(w, seen, R, g0, n, cur=cur)[0] == want_info
+        info, ev = e.poll_leaders(g0, n)
+        assert info == want_info
+        same(ev, want_ev, "one poll")
+        assert np.array_equal(e.read_watch(), seen)
+        # from a fresh seen in two parts
+        e.write_watch(WM.fresh(G))
+        seen, parts = WM.fresh(G), []
+        for room in (total // 2, total):
+            m_info, m_ev, _ = WM.poll(w, seen, R, g0, n, room, cur=cur)
+            info, ev = e.poll_leaders(g0, n, room)
+            assert info == m_info, (room, info, m_info)
+            same(ev, m_ev, f"max_events {room}")
+            assert np.array_equal(e.read_watch(), seen)
+            parts.append(ev)
+        assert [len(p) for p in parts] == [total // 2, total - total // 2]
+        same(np.concatenate(parts), want_ev, "the two parts")
+        # the _dev form
+        e.write_watch(WM.fresh(G))
+        buf = torch.full(((total + 1) * 6,), -7, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        assert e.poll_leaders_dev(buf.data_ptr(), total, g0, n) == want_info
+        raw = buf.cpu().numpy()
+        same(raw[:total * 6].view(abi.EVENT_DTYPE), want_ev, "device events")
+        assert (raw[total * 6:] == -7).all()
+        assert np.array_equal(e.read_watch(), seen)
 
 
 def test_host_device_and_peek_forms_agree():
