@@ -53,8 +53,8 @@ extern "C" {
  * raft_engine_evacuate*), leader no-op entries (raft_engine_append_noops*,
  * raft_engine_sm_set_noop), the leader watch (raft_engine_poll_leaders*,
  * raft_engine_read_watch / write_watch), the proposal outbox
- * (raft_engine_outbox_*, raft_outbox_submit*) and the safety audit
- * (raft_audit_*) */
+ * (raft_engine_outbox_*, raft_outbox_submit*), the safety audit
+ * (raft_audit_*) and the liveness monitor (raft_monitor_*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -1469,6 +1469,172 @@ int raft_audit_report_dev(raft_audit* a, int64_t g0, int64_t n, raft_audit_event
                           raft_audit_report_info* info);
 int raft_audit_read (raft_audit* a, int64_t g0, int64_t n, int32_t* out);
 int raft_audit_write(raft_audit* a, int64_t g0, int64_t n, const int32_t* in);
+
+/* ---- the liveness monitor: outages, stalled commits and lag over time ---------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The audit above answers "did a group ever do something forbidden".  The
+ * monitor answers the other half: which groups make no progress now, for how
+ * long, and why -- so that raft_engine_append_noops, raft_engine_install_snapshot
+ * and the transfers can be aimed at the groups that need them.
+ * RAFT_C_GROUPS_WITH_LEADER is one number per step for the whole engine; the
+ * monitor keeps, per group, since when it is down, and for the engine a
+ * histogram of the lengths of the outages that ended.  The reference has no
+ * counterpart.
+ *
+ * - A raft_monitor belongs to one engine and owns its HBM
+ *   (raft_monitor_device_bytes: 64 G bytes of ledger rounded up to 256, and 512
+ *   for the availability totals; raft_engine_device_bytes does not count it).
+ *   The engine does not know about it: the step kernel, the canonical state,
+ *   the digest and every other call are as before, raft_engine_reset does NOT
+ *   reach it (call raft_monitor_reset), and it is destroyed before its engine.
+ *   observe and report never write engine memory.
+ * - The thresholds are fixed at create (raft_monitor_config).  RAFT_EINVAL: a
+ *   null argument, a negative threshold, nonzero reserved, churn_terms > 0 with
+ *   churn_steps < 1.
+ * - The ledger of one group, 16 int32 words (64 bytes, whatever R) as
+ *   raft_monitor_read returns it:
+ *     [0]  now          RAFT_MONITOR_* bits true at the last observe          0
+ *     [1]  ever         the sticky OR of every now                            0
+ *     [2]  first_step   step index (low 32 bits) of the observe where ever
+ *                       left 0                                                0
+ *     [3]  leader       the newest leader at the last observe                 -1
+ *     [4]  down_since   step index of the observe that first saw the running
+ *                       outage                                                -1
+ *     [5]  outages      outages that have ended (saturating)                  0
+ *     [6]  down_total   the sum of their lengths in steps (saturating)        0
+ *     [7]  longest      the longest of them                                   0
+ *     [8]  stall_since  step index at which the running backlog last advanced -1
+ *     [9]  stall_mark   the leader's committed prefix at that moment          0
+ *     [10] win_start    the churn window's first step                         -1
+ *     [11] win_term     the group's highest term at win_start                 0
+ *     [12] lag_mask     bit r: replica r is lagging                           0
+ *     [13] max_lag      the largest lag among the group's replicas            0
+ *     [14], [15]        reserved                                              0
+ *   (last column: the zero state of create and reset).
+ * - One observe of one group, in this order; "old" is the ledger before the
+ *   call.  s is the low 32 bits of raft_engine_step_index;
+ *   age(x) = max(0, (int32)(s - x)) with the subtraction taken mod 2^32 (a step
+ *   index that went backwards gives 0); L is the newest leader by
+ *   raft_read_begin_batch's rule (role LEADER, the highest currentTerm, the
+ *   lowest index among equals; -1 if none);
+ *   hi_r = min(commitIndex_r, lastIndex_r) within 0..log_cap;
+ *   T = max_r currentTerm_r.
+ *   1. Outage.  L == -1: down_since = s if it was -1; LEADERLESS iff
+ *      age(down_since) >= leaderless_steps.  L >= 0 and old down_since != -1: an
+ *      outage ended, len = max(1, age(old down_since)); outages += 1,
+ *      down_total += len, longest = max(longest, len), down_since = -1, and the
+ *      monitor's availability totals get hist[floor(log2(len))] += 1,
+ *      outages += 1, down_steps += len.  A fresh engine's wait for its first
+ *      leader is an outage like any other.
+ *   2. Stalled commit.  backlog = L >= 0 and lastIndex_L > hi_L.  No backlog:
+ *      stall_since = -1, stall_mark = 0.  Backlog, and old stall_since == -1 or
+ *      hi_L > old stall_mark: stall_since = s, stall_mark = hi_L.  Otherwise
+ *      both stay: a new leader whose commit point is below the mark has not
+ *      advanced anything.  COMMIT_STALLED iff backlog and
+ *      age(stall_since) >= stalled_steps.  (What raft_engine_append_noops
+ *      frees: a textbook leader whose log ends with an entry of an earlier
+ *      term never commits it while idle.)
+ *   3. Lag.  With lag_entries > 0 and L >= 0: lag_r = lastIndex_L - lastIndex_r
+ *      for r != L; lag_mask has bit r iff lag_r >= lag_entries;
+ *      max_lag = max(0, max_r lag_r) (at most 2^31 - 1); LAGGING iff
+ *      lag_mask != 0.  Otherwise both words are 0.  (What
+ *      raft_engine_install_snapshot(..., min_lag) heals.)
+ *   4. Churn, only with churn_terms > 0.  If win_start == -1:
+ *      (win_start, win_term) = (s, T).  CHURNING iff T - win_term >= churn_terms.
+ *      Then, if age(win_start) >= churn_steps: (win_start, win_term) = (s, T).
+ *   5. now = the bits above, ever |= now, first_step = s when ever leaves 0,
+ *      leader = L.
+ *   -1 means "none" in down_since, stall_since and win_start: an observe at a
+ *   step index whose low 32 bits are 0xFFFFFFFF stores what reads as none.
+ *   The rules read three state quads per replica (term and role, lastIndex,
+ *   commitIndex) and no log slot: a log_window changes nothing and there is no
+ *   `unknown` count.
+ * - raft_monitor_report lists the groups of the range with (word & kinds) != 0
+ *   -- word is now (RAFT_MONITOR_NOW) or ever (RAFT_MONITOR_EVER) -- in
+ *   ascending group order, cut at max_events; `pending` counts the rest.  It
+ *   consumes nothing; max_events == 0 (with or without a buffer) is a peek.
+ *   RAFT_EINVAL also for another `which` and for bits in kinds outside
+ *   RAFT_MONITOR_ALL.
+ * - raft_monitor_get_availability / _set_availability read and resume the
+ *   totals (hist[k]: ended outages of 2^k .. 2^(k+1) - 1 steps); a negative word
+ *   or nonzero reserved: RAFT_EINVAL, nothing stored.
+ * - raft_monitor_write resumes ledgers.  RAFT_EINVAL with nothing stored:
+ *   unknown bits in now or ever, leader outside -1..R-1, lag_mask bits at or
+ *   above R, negative outages, down_total, longest, max_lag or stall_mark,
+ *   nonzero reserved words.  No ledger word is ever used as an index.
+ * RAFT_EINVAL: null handle or info, max_events < 0, out == NULL with
+ * max_events > 0, a _dev buffer that is not 16-byte aligned; RAFT_ERANGE:
+ * groups outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Both protocol modes and every log layout.  The rules see sampled instants:
+ * an outage's length is measured between the observe that first saw no leader
+ * and the observe that first saw one again, a leader lost and regained between
+ * two observes is never seen, and observing every k steps measures in units of
+ * k.  Observed after every step with leaderless_steps = 0, info.leaderless is
+ * G - RAFT_C_GROUPS_WITH_LEADER of that step.
+ *
+ * Ordering is raft_engine_drain_committed's: every call runs on the engine
+ * stream, sees every step enqueued before it, later step launches wait for
+ * it, and it returns when its kernels have finished. */
+#define RAFT_MONITOR_LEADERLESS     (1 << 0)  /* no LEADER for leaderless_steps steps or more */
+#define RAFT_MONITOR_COMMIT_STALLED (1 << 1)  /* the leader's backlog has not advanced for stalled_steps steps */
+#define RAFT_MONITOR_LAGGING        (1 << 2)  /* a replica is lag_entries or more behind the newest leader */
+#define RAFT_MONITOR_CHURNING       (1 << 3)  /* the highest term rose by churn_terms within a window */
+#define RAFT_MONITOR_ALL            15
+#define RAFT_MONITOR_NOW  0
+#define RAFT_MONITOR_EVER 1
+typedef struct raft_monitor raft_monitor;
+typedef struct raft_monitor_config {     /* 32 bytes */
+    int32_t leaderless_steps;  /* LEADERLESS once a group has shown no LEADER for this many steps (0: at once) */
+    int32_t stalled_steps;     /* COMMIT_STALLED once a backlog has not advanced for this many steps */
+    int32_t lag_entries;       /* LAGGING: a replica this many entries behind the newest leader (0: off) */
+    int32_t churn_terms;       /* CHURNING: the group's highest term rose by this much within a window (0: off) */
+    int32_t churn_steps;       /* the window's length in steps (>= 1 when churn_terms > 0) */
+    int32_t reserved[3];       /* 0 */
+} raft_monitor_config;
+typedef struct raft_monitor_info {       /* 96 bytes */
+    int64_t flagged;           /* groups of the range with now != 0 after the call */
+    int64_t newly_flagged;     /* old now == 0, now != 0 */
+    int64_t cleared;           /* old now != 0, now == 0 */
+    int64_t leaderless;        /* groups with the bit in now, per kind */
+    int64_t commit_stalled;
+    int64_t lagging;
+    int64_t churning;
+    int64_t down;              /* groups with down_since != -1 after the call (flagged or not yet) */
+    int64_t outages_ended;     /* by this call */
+    int64_t down_steps_ended;  /* the sum of their lengths */
+    int64_t reserved[2];       /* 0 */
+} raft_monitor_info;
+typedef struct raft_monitor_event {      /* 32 bytes */
+    int64_t group;             /* engine-local group index */
+    int32_t now, ever, down_since, stall_since, leader, lag_mask;
+} raft_monitor_event;
+typedef struct raft_monitor_report_info {  /* 64 bytes */
+    int64_t delivered;         /* events written to out */
+    int64_t pending;           /* listed groups beyond max_events (all of them, in a peek) */
+    int64_t flagged;           /* delivered + pending */
+    int64_t reserved[5];       /* 0 */
+} raft_monitor_report_info;
+typedef struct raft_monitor_availability {  /* 288 bytes */
+    int64_t hist[32];          /* hist[k]: ended outages whose length in steps has floor(log2) == k */
+    int64_t outages;           /* ended outages */
+    int64_t down_steps;        /* the sum of their lengths */
+    int64_t reserved[2];       /* 0 */
+} raft_monitor_availability;
+int raft_monitor_create (raft_engine* e, const raft_monitor_config* cfg, raft_monitor** out);
+int raft_monitor_destroy(raft_monitor* m);
+int raft_monitor_reset  (raft_monitor* m);
+int64_t raft_monitor_device_bytes(raft_monitor* m);
+int raft_monitor_observe(raft_monitor* m, int64_t g0, int64_t n, raft_monitor_info* info);
+int raft_monitor_report    (raft_monitor* m, int64_t g0, int64_t n, int32_t which, int32_t kinds,
+                            raft_monitor_event* out_host, int64_t max_events, raft_monitor_report_info* info);
+int raft_monitor_report_dev(raft_monitor* m, int64_t g0, int64_t n, int32_t which, int32_t kinds,
+                            raft_monitor_event* out_dev, int64_t max_events, raft_monitor_report_info* info);
+int raft_monitor_get_availability(raft_monitor* m, raft_monitor_availability* out);
+int raft_monitor_set_availability(raft_monitor* m, const raft_monitor_availability* in);
+int raft_monitor_read (raft_monitor* m, int64_t g0, int64_t n, int32_t* out);
+int raft_monitor_write(raft_monitor* m, int64_t g0, int64_t n, const int32_t* in);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

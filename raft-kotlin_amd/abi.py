@@ -385,6 +385,51 @@ def audit_words(R: int) -> int:
     return AUDIT_HEAD + 2 * R
 
 
+class raft_monitor_config(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("leaderless_steps", "stalled_steps", "lag_entries", "churn_terms",
+                                         "churn_steps")] + [("reserved", C.c_int32 * 3)]
+
+
+class raft_monitor_info(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("flagged", "newly_flagged", "cleared", "leaderless", "commit_stalled", "lagging",
+                                         "churning", "down", "outages_ended", "down_steps_ended")] + [
+        ("reserved", C.c_int64 * 2)]
+
+
+class raft_monitor_event(C.Structure):
+    _fields_ = [("group", C.c_int64)] + [(k, C.c_int32) for k in ("now", "ever", "down_since", "stall_since", "leader",
+                                                                  "lag_mask")]
+
+
+class raft_monitor_report_info(C.Structure):
+    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("flagged", C.c_int64), ("reserved", C.c_int64 * 5)]
+
+
+class raft_monitor_availability(C.Structure):
+    _fields_ = [("hist", C.c_int64 * 32), ("outages", C.c_int64), ("down_steps", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+# the liveness monitor (raft_monitor_*): the bits of a ledger's now / ever words in the order of raft_monitor_info's
+# per-kind counts, the report's word selector, raft_monitor_event as a numpy record (32 bytes, no padding), the
+# thresholds of a config, the names of a group's 16 exported ledger words
+MONITOR_LEADERLESS, MONITOR_COMMIT_STALLED, MONITOR_LAGGING, MONITOR_CHURNING = 1, 2, 4, 8
+MONITOR_KINDS = ("leaderless", "commit_stalled", "lagging", "churning")
+MONITOR_ALL = 15
+MONITOR_NOW, MONITOR_EVER = 0, 1
+MONITOR_INFO_FIELDS = ("flagged", "newly_flagged", "cleared") + MONITOR_KINDS + ("down", "outages_ended",
+                                                                               "down_steps_ended")
+MONITOR_REPORT_FIELDS = ("delivered", "pending", "flagged")
+MONITOR_EVENT_DTYPE = np.dtype([("group", np.int64), ("now", np.int32), ("ever", np.int32), ("down_since", np.int32),
+                                ("stall_since", np.int32), ("leader", np.int32), ("lag_mask", np.int32)])
+MONITOR_CONFIG_FIELDS = ("leaderless_steps", "stalled_steps", "lag_entries", "churn_terms", "churn_steps")
+MONITOR_STALLED_STEPS = 16   # RaftEngine.monitor's default stalled_steps
+MONITOR_WORD_NAMES = ("now", "ever", "first_step", "leader", "down_since", "outages", "down_total", "longest",
+                      "stall_since", "stall_mark", "win_start", "win_term", "lag_mask", "max_lag", "reserved0",
+                      "reserved1")
+MONITOR_WORDS = 16
+MONITOR_HIST = 32
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -577,6 +622,18 @@ def load_library(path: str | None = None):
         "raft_audit_report_dev": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p, I64, P(raft_audit_report_info)]),
         "raft_audit_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
         "raft_audit_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
+        "raft_monitor_create": (C.c_int, [eng, P(raft_monitor_config), P(C.c_void_p)]),
+        "raft_monitor_destroy": (C.c_int, [C.c_void_p]),
+        "raft_monitor_reset": (C.c_int, [C.c_void_p]),
+        "raft_monitor_device_bytes": (I64, [C.c_void_p]),
+        "raft_monitor_observe": (C.c_int, [C.c_void_p, I64, I64, P(raft_monitor_info)]),
+        "raft_monitor_report": (C.c_int, [C.c_void_p, I64, I64, I32, I32, C.c_void_p, I64, P(raft_monitor_report_info)]),
+        "raft_monitor_report_dev": (C.c_int, [C.c_void_p, I64, I64, I32, I32, C.c_void_p, I64,
+                                              P(raft_monitor_report_info)]),
+        "raft_monitor_get_availability": (C.c_int, [C.c_void_p, P(raft_monitor_availability)]),
+        "raft_monitor_set_availability": (C.c_int, [C.c_void_p, P(raft_monitor_availability)]),
+        "raft_monitor_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
+        "raft_monitor_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -644,6 +701,9 @@ EXPORTED_SYMBOLS = [
     "raft_engine_outbox_pump_dev", "raft_engine_outbox_read", "raft_engine_outbox_write",
     "raft_audit_create", "raft_audit_destroy", "raft_audit_reset", "raft_audit_device_bytes", "raft_audit_observe",
     "raft_audit_report", "raft_audit_report_dev", "raft_audit_read", "raft_audit_write",
+    "raft_monitor_create", "raft_monitor_destroy", "raft_monitor_reset", "raft_monitor_device_bytes",
+    "raft_monitor_observe", "raft_monitor_report", "raft_monitor_report_dev", "raft_monitor_get_availability",
+    "raft_monitor_set_availability", "raft_monitor_read", "raft_monitor_write",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

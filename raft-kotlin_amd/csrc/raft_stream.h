@@ -2,7 +2,7 @@
 // paths that hand the host an ordered stream of records, cut at a room limit,
 // share.  Included by the side-path files only (never by raft_engine.hip: it
 // is not one of the step kernel's sources):
-//   raft_watch.hip, raft_audit.hip    a source object each, and the driver
+//   raft_watch.hip, raft_audit.hip, raft_monitor.hip   a source object each, and the driver
 //   raft_apply.hip, raft_outbox.hip   the scan scratch, the record buffer, the publish / the tally
 //   raft_fault.hip, raft_snapshot.hip, raft_transfer.hip, raft_noop.hip, raft_sm.hip   the striped tally
 // The source-object contract of the flag and write kernels is below and in

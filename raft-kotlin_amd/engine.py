@@ -61,30 +61,15 @@ class RaftComm:
             pass
 
 
-class RaftAudit:
-    """A safety audit of one engine (include/raft_engine.h raft_audit_*): a
-    ledger per group in HBM of its own, and `observe`, which checks the state
-    now against it -- a term that went backwards, a vote changed within a
-    term, two leaders of one term, a committed entry that changed, a newer
-    leader that lacks it.  Made by RaftEngine.audit(); close it before its
-    engine.  RaftEngine.reset does not reach it: call reset() here."""
-
-    def __init__(self, engine: "RaftEngine"):
-        self._lib, self.engine = engine._lib, engine
-        self.R, self.G = engine.R, engine.G
-        self.words = abi.audit_words(self.R)
-        h = C.c_void_p()
-        engine._check(self._lib.raft_audit_create(engine._h, C.byref(h)), "raft_audit_create")
-        self._h = h
+class _GroupLedger:
+    """What the handles that keep a ledger per group beside an engine share
+    (RaftAudit, RaftMonitor): the error check, the group-range and max_events
+    arguments, and closing on exit or collection.  A subclass sets _lib, _h and
+    G and has close()."""
 
     def _check(self, rc: int, what: str):
         if rc != abi.RAFT_OK:
             raise RaftError(f"{what} failed ({rc}): " + self._lib.raft_last_error().decode(errors="replace"))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.raft_audit_destroy(self._h)                     # (RaftEngine.close closes its audits first)
-            self._h = None
 
     def __del__(self):
         try:
@@ -104,6 +89,34 @@ class RaftAudit:
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
                 raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
         return int(g0), int(n)
+
+    @staticmethod
+    def _room(max_events, what: str):
+        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
+                                       or max_events < 0):
+            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
+
+
+class RaftAudit(_GroupLedger):
+    """A safety audit of one engine (include/raft_engine.h raft_audit_*): a
+    ledger per group in HBM of its own, and `observe`, which checks the state
+    now against it -- a term that went backwards, a vote changed within a
+    term, two leaders of one term, a committed entry that changed, a newer
+    leader that lacks it.  Made by RaftEngine.audit(); close it before its
+    engine.  RaftEngine.reset does not reach it: call reset() here."""
+
+    def __init__(self, engine: "RaftEngine"):
+        self._lib, self.engine = engine._lib, engine
+        self.R, self.G = engine.R, engine.G
+        self.words = abi.audit_words(self.R)
+        h = C.c_void_p()
+        engine._check(self._lib.raft_audit_create(engine._h, C.byref(h)), "raft_audit_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.raft_audit_destroy(self._h)                     # (RaftEngine.close closes its audits first)
+            self._h = None
 
     @property
     def device_bytes(self) -> int:
@@ -128,12 +141,6 @@ class RaftAudit:
         ri = abi.raft_audit_report_info()
         self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(ri)), what)
         return {k: int(getattr(ri, k)) for k in abi.AUDIT_REPORT_FIELDS}
-
-    @staticmethod
-    def _room(max_events, what: str):
-        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
-                                       or max_events < 0):
-            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
 
     def report(self, g0: int = 0, n: int | None = None, max_events: int | None = None):
         """raft_audit_report: (info, events) -- the groups of [g0, g0 + n) with
@@ -182,6 +189,138 @@ class RaftAudit:
         self._check(self._lib.raft_audit_write(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "raft_audit_write")
 
 
+class RaftMonitor(_GroupLedger):
+    """A liveness monitor of one engine (include/raft_engine.h raft_monitor_*):
+    a 16-word ledger per group in HBM of its own, and `observe`, which brings it
+    up to date from the state now -- since when the group has no leader, since
+    when its leader's backlog has not advanced, which replicas lag, whether its
+    terms churn -- and keeps a histogram of the lengths of the outages that
+    ended.  Made by RaftEngine.monitor(); close it before its engine.
+    RaftEngine.reset does not reach it: call reset() here."""
+
+    def __init__(self, engine: "RaftEngine", **thresholds):
+        self._lib, self.engine = engine._lib, engine
+        self.R, self.G = engine.R, engine.G
+        self.words = abi.MONITOR_WORDS
+        cfg = abi.raft_monitor_config()
+        for k, v in thresholds.items():
+            if k not in abi.MONITOR_CONFIG_FIELDS:
+                raise TypeError(f"monitor: unknown threshold {k!r}")
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 31:
+                raise ValueError(f"monitor: {k} must be an integer in 0..2^31-1, not {v!r}")
+            setattr(cfg, k, int(v))
+        self.config = {k: int(getattr(cfg, k)) for k in abi.MONITOR_CONFIG_FIELDS}
+        h = C.c_void_p()
+        engine._check(self._lib.raft_monitor_create(engine._h, C.byref(cfg), C.byref(h)), "raft_monitor_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.raft_monitor_destroy(self._h)                   # (RaftEngine.close closes its monitors first)
+            self._h = None
+
+    @property
+    def device_bytes(self) -> int:
+        """HBM owned by the monitor (RaftEngine.device_bytes does not count it)."""
+        return int(self._lib.raft_monitor_device_bytes(self._h))
+
+    def reset(self):
+        """Every ledger and the availability totals back to their zero state (as created)."""
+        self._check(self._lib.raft_monitor_reset(self._h), "monitor reset")
+
+    def observe(self, g0: int = 0, n: int | None = None) -> dict:
+        """raft_monitor_observe of groups [g0, g0 + n): bring their ledgers up
+        to date from the state now.  Returns flagged, newly_flagged, cleared,
+        one count per kind (abi.MONITOR_KINDS) of the groups that carry the bit
+        now, down (groups without a leader, flagged or not yet), and the
+        outages that ended in this call with the sum of their lengths."""
+        g0, n = self._range(g0, n, "observe")
+        mi = abi.raft_monitor_info()
+        self._check(self._lib.raft_monitor_observe(self._h, g0, n, C.byref(mi)), "raft_monitor_observe")
+        return {k: int(getattr(mi, k)) for k in abi.MONITOR_INFO_FIELDS}
+
+    def _which(self, ever: bool, kinds, what: str):
+        kinds = abi.MONITOR_ALL if kinds is None else kinds
+        if isinstance(kinds, bool) or not isinstance(kinds, (int, np.integer)) or kinds & ~abi.MONITOR_ALL:
+            raise ValueError(f"{what}: kinds must be None or an OR of abi.MONITOR_* bits, not {kinds!r}")
+        return abi.MONITOR_EVER if ever else abi.MONITOR_NOW, int(kinds)
+
+    def _report(self, fn, g0, n, which, kinds, out_ptr, room, what: str) -> dict:
+        ri = abi.raft_monitor_report_info()
+        self._check(fn(self._h, g0, n, which, kinds, C.c_void_p(out_ptr or 0), int(room), C.byref(ri)), what)
+        return {k: int(getattr(ri, k)) for k in abi.MONITOR_REPORT_FIELDS}
+
+    def report(self, g0: int = 0, n: int | None = None, max_events: int | None = None, *, ever: bool = False,
+               kinds: int | None = None):
+        """raft_monitor_report: (info, events) -- the groups of [g0, g0 + n)
+        whose `now` word (ever=True: whose sticky `ever` word) has a bit of
+        `kinds` (None: any), as a numpy array of abi.MONITOR_EVENT_DTYPE (group,
+        now, ever, down_since, stall_since, leader, lag_mask) in ascending group
+        order, at most max_events of them (None: all of them; 0: a peek).  info:
+        delivered, pending, flagged.  Nothing is consumed."""
+        g0, n = self._range(g0, n, "report")
+        self._room(max_events, "report")
+        which, kinds = self._which(ever, kinds, "report")
+        fn = self._lib.raft_monitor_report
+        if max_events is None:
+            max_events = self._report(fn, g0, n, which, kinds, 0, 0, "raft_monitor_report")["pending"]
+        out = np.zeros(max(1, int(max_events)), dtype=abi.MONITOR_EVENT_DTYPE)
+        info = self._report(fn, g0, n, which, kinds, out.ctypes.data, int(max_events), "raft_monitor_report")
+        return info, out[: info["delivered"]]
+
+    def report_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None, *, ever: bool = False,
+                   kinds: int | None = None) -> dict:
+        """report into a DEVICE buffer of max_events 32-byte records (16-byte
+        aligned); returns the info once the kernels finished."""
+        g0, n = self._range(g0, n, "report_dev")
+        self._room(max_events, "report_dev")
+        which, kinds = self._which(ever, kinds, "report_dev")
+        if max_events is None or (max_events > 0 and not out_ptr):
+            raise ValueError("report_dev: a device buffer and its max_events are required")
+        if out_ptr % 16:
+            raise ValueError("report_dev: the record buffer must be 16-byte aligned")
+        return self._report(self._lib.raft_monitor_report_dev, g0, n, which, kinds, out_ptr, max_events,
+                            "raft_monitor_report_dev")
+
+    def availability(self) -> dict:
+        """raft_monitor_get_availability: hist ([32] int64; hist[k] counts the
+        ended outages of 2^k .. 2^(k+1) - 1 steps), outages, down_steps."""
+        av = abi.raft_monitor_availability()
+        self._check(self._lib.raft_monitor_get_availability(self._h, C.byref(av)), "raft_monitor_get_availability")
+        return {"hist": np.array(av.hist[:], dtype=np.int64), "outages": int(av.outages), "down_steps": int(av.down_steps)}
+
+    def set_availability(self, hist, outages: int, down_steps: int):
+        """raft_monitor_set_availability (resuming a monitor): the library
+        refuses a negative total and stores nothing then."""
+        h = np.asarray(hist)
+        if h.shape != (abi.MONITOR_HIST,) or h.dtype.kind not in "iu":
+            raise ValueError(f"set_availability: hist {h.shape} {h.dtype} must be {abi.MONITOR_HIST} integers")
+        av = abi.raft_monitor_availability()
+        av.hist[:] = [int(x) for x in h]
+        av.outages, av.down_steps = int(outages), int(down_steps)
+        self._check(self._lib.raft_monitor_set_availability(self._h, C.byref(av)), "raft_monitor_set_availability")
+
+    def read(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """The ledgers of groups [g0, g0 + n): [n, 16] int32 (abi.MONITOR_WORD_NAMES)."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(int(n), 0), self.words), dtype=np.int32)   # a bad range is the library's to refuse
+        self._check(self._lib.raft_monitor_read(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "raft_monitor_read")
+        return out
+
+    def write(self, ledger: np.ndarray, g0: int = 0):
+        """Store the ledgers of groups [g0, g0 + len(ledger)) (resuming a
+        monitor): an integer [n, 16] array.  The library refuses unknown bits in
+        now or ever, a leader outside -1..R-1, lag_mask bits at or above R, a
+        negative count and nonzero reserved words, and stores nothing then."""
+        a = np.asarray(ledger)
+        if a.ndim != 2 or a.shape[1] != self.words or a.dtype.kind not in "iu":
+            raise ValueError(f"monitor write: ledger {a.shape} {a.dtype} must be an integer array of shape "
+                             f"(n, {self.words})")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        self._check(self._lib.raft_monitor_write(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)),
+                    "raft_monitor_write")
+
+
 class RaftEngine:
     def __init__(self, params: abi.raft_params, device: int = 0):
         self._lib = abi.load_library()
@@ -204,7 +343,7 @@ class RaftEngine:
 
     def close(self):
         if getattr(self, "_h", None):
-            for ref in getattr(self, "_audits", ()):                  # an audit goes before its engine
+            for ref in (*getattr(self, "_audits", ()), *getattr(self, "_monitors", ())):   # they go before their engine
                 a = ref()
                 if a is not None:
                     a.close()
@@ -1022,6 +1161,25 @@ class RaftEngine:
             self._audits = []
         self._audits.append(weakref.ref(a))
         return a
+
+    # -- the liveness monitor (raft_monitor_*) ------------------------------------------------------------
+    def monitor(self, leaderless_steps: int = 0, stalled_steps: int = abi.MONITOR_STALLED_STEPS, lag_entries: int = 0,
+                churn_terms: int = 0, churn_steps: int = 1) -> RaftMonitor:
+        """A new liveness monitor of this engine, every ledger in its zero state
+        (RaftMonitor: observe, report, report_dev, read, write, reset,
+        availability, set_availability, device_bytes, close).  A group is
+        LEADERLESS once it has shown no leader for leaderless_steps steps,
+        COMMIT_STALLED once its leader's backlog has not advanced for
+        stalled_steps, LAGGING while a replica is lag_entries or more behind the
+        newest leader (0: off), CHURNING when its highest term rose by
+        churn_terms within a window of churn_steps (0: off).  Closing the engine
+        closes its monitors first."""
+        m = RaftMonitor(self, leaderless_steps=leaderless_steps, stalled_steps=stalled_steps, lag_entries=lag_entries,
+                        churn_terms=churn_terms, churn_steps=churn_steps)
+        if not hasattr(self, "_monitors"):
+            self._monitors = []
+        self._monitors.append(weakref.ref(m))
+        return m
 
     # -- the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*) ---------------------------------
     def outbox_configure(self, capacity: int, expire_steps: int = 0):

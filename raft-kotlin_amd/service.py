@@ -37,6 +37,10 @@ argument meaning and error behaviour:
 * ``RaftService.check_safety`` / ``violations``: the engine's safety audit --
   Raft's invariants checked over time on the device, and the groups that
   broke one, with the step at which it was first seen
+* ``RaftService.check_liveness`` / ``unavailable`` / ``remediate``: the engine's
+  liveness monitor -- which groups have no leader, a stalled commit or a
+  lagging replica now and since when, and the no-ops and snapshot installs
+  aimed at exactly those
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -471,6 +475,52 @@ class RaftService:
         if getattr(self, "safety_audit", None) is None:
             return np.zeros(0, dtype=abi.AUDIT_EVENT_DTYPE)
         return self.safety_audit.report(max_events=max_events)[1]
+
+    # -- the liveness monitor: which groups make no progress now, for how long, and why -----------------
+    def check_liveness(self, g0: int = 0, n: Optional[int] = None) -> dict:
+        """Observe groups [g0, g0 + n) with this service's liveness monitor
+        (``liveness_monitor``; RaftEngine.monitor() with its defaults, made at
+        the first call unless the caller stored one with thresholds of its
+        own).  Returns the observe's info -- flagged, newly_flagged, cleared,
+        one count per kind (abi.MONITOR_KINDS), down, outages_ended,
+        down_steps_ended; ``last_liveness`` keeps it with the range.  After
+        RaftEngine.reset call ``liveness_monitor.reset()`` too."""
+        if getattr(self, "liveness_monitor", None) is None:
+            self.liveness_monitor = self.engine.monitor()
+        info = self.liveness_monitor.observe(g0, n)
+        self.last_liveness = (info, int(g0), self.engine.G - int(g0) if n is None else int(n))
+        return info
+
+    def unavailable(self, kinds: Optional[int] = None, max_events: Optional[int] = None) -> np.ndarray:
+        """The groups the last check_liveness found stuck (abi.MONITOR_EVENT_DTYPE:
+        group, now, ever, down_since, stall_since, leader, lag_mask) with a bit
+        of `kinds` (an OR of abi.MONITOR_*; None: any) in `now`, in ascending
+        group order, at most max_events of them.  Nothing is consumed; empty
+        before the first check_liveness."""
+        if getattr(self, "liveness_monitor", None) is None:
+            return np.zeros(0, dtype=abi.MONITOR_EVENT_DTYPE)
+        return self.liveness_monitor.report(max_events=max_events, kinds=kinds)[1]
+
+    def remediate(self) -> dict:
+        """Aim the engine's remedies at what the last check_liveness counted,
+        over its range: if it counted commit_stalled groups and the engine runs
+        in textbook mode, assert_leadership (a leader's no-op entry frees a
+        commit an election left stuck); if it counted lagging groups and the
+        machine is configured, heal's apply_committed and install_snapshot with
+        min_lag = the monitor's lag_entries.  Returns {"noops": info or None,
+        "install": info or None}.  The engine is never stepped: the remedies
+        take effect in the caller's next steps."""
+        out = {"noops": None, "install": None}
+        if getattr(self, "last_liveness", None) is None:
+            return out
+        info, g0, n = self.last_liveness
+        e = self.engine
+        if info["commit_stalled"] and int(e.p.mode) == abi.MODE_TEXTBOOK:
+            out["noops"] = self.assert_leadership(g0, n)
+        if info["lagging"] and e.sm_slots:
+            self.last_heal_apply = self.apply_committed(g0, n)
+            out["install"] = e.install_snapshot(g0=g0, n=n, min_lag=self.liveness_monitor.config["lag_entries"])
+        return out
 
     def submit(self, groups, commands: List[str]) -> np.ndarray:
         """One command per entry of `groups`, routed to each group's leader in
