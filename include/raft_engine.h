@@ -1636,6 +1636,128 @@ int raft_monitor_set_availability(raft_monitor* m, const raft_monitor_availabili
 int raft_monitor_read (raft_monitor* m, int64_t g0, int64_t n, int32_t* out);
 int raft_monitor_write(raft_monitor* m, int64_t g0, int64_t n, const int32_t* in);
 
+/* ---- the persistence stream: hard state and new log entries as a delta ----------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * What a replica must make durable before its answers count: currentTerm,
+ * votedFor and the log entries it gained or replaced since the last poll --
+ * etcd's Ready.HardState and Ready.Entries, beside Ready.CommittedEntries
+ * (raft_engine_drain_committed) and SoftState (raft_engine_poll_leaders).  It
+ * is what raft_engine_restart's "term, vote and log persist" stands on: a host
+ * that applies the stream to an image can write a replica back after
+ * RAFT_RESTART_AMNESIA, keep a write-ahead log, or keep a second engine in
+ * step, without copying every log row.  The reference persists nothing.
+ *
+ * - A raft_wal belongs to one engine and owns its HBM (raft_wal_device_bytes:
+ *   24 G R bytes of cursors rounded up to 256; raft_engine_device_bytes does not
+ *   count it).  The engine does not know about it: the step kernel, the
+ *   canonical state, the digest and every other call are as before,
+ *   raft_engine_reset does NOT reach it (call raft_wal_reset), and it is
+ *   destroyed before its engine.  A poll never writes engine memory.
+ * - The cursor of one replica (raft_wal_cursor, 24 bytes; fresh: 0, -1, 0, 0, 0):
+ *     term, vote    the hard state last handed out
+ *     stable        a count, like commitIndex: entries [0, stable) have been
+ *                   handed out as they were at the time
+ *     stable_term   the term of entry stable - 1 as handed out (0 at stable 0)
+ *     floor         a count <= stable: entries [0, floor) were committed on
+ *                   this replica when handed out
+ * - A poll visits the selected replicas of groups [g0, g0 + n) (replica = -1:
+ *   every replica, else that index of each group).  For each, with the state
+ *   now, last = clamp(lastIndex, 0, log_cap), hi the committed prefix of
+ *   raft_engine_drain_committed and, with a log_window W,
+ *   wl = max(0, physLen - W) (else 0):
+ *   the replica is CLEAN when stable <= last and either stable == 0 or slot
+ *   stable - 1 is readable (>= wl) and log[stable - 1].term == stable_term.
+ *   1. If (currentTerm, votedFor) != (term, vote): one RAFT_WAL_HARDSTATE.
+ *   2. If not clean: keep = min(floor, last); keep < floor means committed
+ *      entries vanished (amnesia, reference-mode quirks) and counts the replica
+ *      in `regressed`; one RAFT_WAL_TRUNCATE(keep); from here on stable = keep.
+ *   3. Entries stable .. last - 1 follow, ascending, one RAFT_WAL_ENTRY each.
+ *      On a ring the ones below wl cannot be read: they are counted in `lost`,
+ *      not emitted, and the call returns RAFT_EWINDOW after doing everything
+ *      else (as the drain does).
+ *   Why floor is enough without a shadow copy of the log: by Log Matching two
+ *   logs that agree on the term at one index agree on everything before it,
+ *   so the one comparison at stable - 1 proves that the whole handed-out
+ *   prefix is still the replica's log.  A replica's own committed prefix is
+ *   final in RAFT_MODE_TEXTBOOK, so after any mismatch re-sending from floor is
+ *   always sufficient; it is more than necessary only by the part of the
+ *   uncommitted suffix that did not change.
+ * - Records come in ascending (group, replica) order and, inside a replica, as
+ *   HARDSTATE, TRUNCATE, ENTRY ascending.  When there are more than
+ *   max_records, exactly the first max_records are written (the cut may fall
+ *   anywhere, also between a replica's HARDSTATE and its TRUNCATE) and
+ *   `pending` counts the rest.  The cursor advances only past what was written:
+ *   a written HARDSTATE stores term / vote; a written TRUNCATE stores
+ *   stable = keep and stable_term = log[keep - 1].term (0 at keep == 0 or below
+ *   wl); each written ENTRY moves stable and stable_term.  After the call every
+ *   visited replica whose handed-out prefix is its log -- it was clean, or its
+ *   TRUNCATE was written -- gets floor = min(hi, stable); one whose TRUNCATE
+ *   was cut off keeps its cursor's stable and floor.  With no step in between,
+ *   successive polls concatenated equal one poll with enough room, record for
+ *   record and cursor for cursor (on a ring that lost entries a TRUNCATE whose
+ *   entries were cut off is sent again, and `lost` counts them again).
+ *   out == NULL with max_records == 0 is a peek: nothing is stored, `pending`
+ *   / `lost` / `regressed` say what a poll would see.
+ * - Promised: in RAFT_MODE_TEXTBOOK without RAFT_RESTART_AMNESIA, applying the
+ *   records of successive polls to an empty image (TRUNCATE(keep): drop every
+ *   entry at index >= keep; ENTRY: store at its index) yields exactly the
+ *   replica's currentTerm, votedFor and log [0, lastIndex) as of the last
+ *   poll; on a ring, the retained window of it.  Not promised: in
+ *   RAFT_MODE_REFERENCE (quirks Q1-Q4, Q9 rewrite committed entries and terms
+ *   repeat across leaders) and after an amnesia restart the stream is defined
+ *   and deterministic, and `regressed` says where committed entries vanished,
+ *   but the image may differ from the log below floor.
+ * - raft_wal_read / raft_wal_write export and resume cursors ([n][R], as they
+ *   lie on the device).  raft_wal_write refuses, with RAFT_EINVAL and nothing
+ *   stored: stable outside 0..log_cap, floor outside 0..stable, vote outside
+ *   -1..R (votedFor holds a node id, replica index + 1, RaftServer.kt:193: the
+ *   step kernel stores -1 or 1..R), term < 0, a nonzero pad.  raft_wal_reset:
+ *   every cursor fresh.
+ * RAFT_EINVAL: null handle or info, replica outside -1..R-1, max_records < 0,
+ * out == NULL with max_records > 0, a _dev buffer that is not 8-byte aligned;
+ * RAFT_ERANGE: groups outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Ordering is raft_engine_drain_committed's: every call runs on the engine
+ * stream, sees every step enqueued before it, later step launches wait for
+ * it, and it returns when its kernels have finished (info stays a host
+ * pointer in the _dev variant). */
+#define RAFT_WAL_HARDSTATE 0   /* term = currentTerm, aux = votedFor, index = -1, cmd = 0: persist this pair */
+#define RAFT_WAL_TRUNCATE  1   /* index = keep, the rest 0: drop every persisted entry at index >= keep */
+#define RAFT_WAL_ENTRY     2   /* index, term, cmd as the log holds them, aux = 0: persist this entry */
+typedef struct raft_wal raft_wal;
+typedef struct raft_wal_cursor {   /* 24 bytes */
+    int32_t term, vote, stable, stable_term, floor, pad;
+} raft_wal_cursor;
+typedef struct raft_wal_record {   /* 24 bytes */
+    int32_t  group;                /* engine-local group index */
+    int16_t  replica;
+    int16_t  kind;                 /* RAFT_WAL_* */
+    int32_t  index;
+    int32_t  term;
+    uint32_t cmd;
+    int32_t  aux;
+} raft_wal_record;
+typedef struct raft_wal_info {     /* 56 bytes */
+    int64_t delivered;             /* records written to out */
+    int64_t pending;               /* records left for lack of room (all of them, in a peek) */
+    int64_t hardstates;            /* of the records written, per kind */
+    int64_t truncates;
+    int64_t entries;
+    int64_t lost;                  /* log_window only: entries that left the window unpersisted; skipped */
+    int64_t regressed;             /* selected replicas whose TRUNCATE goes below their floor */
+} raft_wal_info;
+int raft_wal_create (raft_engine* e, raft_wal** out);
+int raft_wal_destroy(raft_wal* w);
+int raft_wal_reset  (raft_wal* w);
+int64_t raft_wal_device_bytes(raft_wal* w);
+int raft_wal_poll    (raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_wal_record* out_host,
+                      int64_t max_records, raft_wal_info* info);
+int raft_wal_poll_dev(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_wal_record* out_dev,
+                      int64_t max_records, raft_wal_info* info);
+int raft_wal_read (raft_wal* w, int64_t g0, int64_t n, raft_wal_cursor* cursors);
+int raft_wal_write(raft_wal* w, int64_t g0, int64_t n, const raft_wal_cursor* cursors);
+
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages
  * to the same (group, dst) are applied in batch order.  Effects on the

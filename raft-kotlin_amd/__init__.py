@@ -8,10 +8,13 @@ is the HIP library ``lib/libraft_engine.so`` behind the C-ABI in
 """
 from . import abi  # noqa: F401
 
-__all__ = ["abi", "RaftEngine", "RaftService"]
+__all__ = ["abi", "RaftEngine", "RaftService", "WalImage"]
 
 
 def __getattr__(name):
+    if name == "WalImage":
+        from .engine import WalImage
+        return WalImage
     if name == "RaftEngine":
         from .engine import RaftEngine
         return RaftEngine

@@ -430,6 +430,32 @@ MONITOR_WORDS = 16
 MONITOR_HIST = 32
 
 
+class raft_wal_cursor(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("term", "vote", "stable", "stable_term", "floor", "pad")]
+
+
+class raft_wal_record(C.Structure):
+    _fields_ = [("group", C.c_int32), ("replica", C.c_int16), ("kind", C.c_int16), ("index", C.c_int32),
+                ("term", C.c_int32), ("cmd", C.c_uint32), ("aux", C.c_int32)]
+
+
+class raft_wal_info(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("delivered", "pending", "hardstates", "truncates", "entries", "lost",
+                                         "regressed")]
+
+
+# the persistence stream (raft_wal_*): the record kinds, raft_wal_record and raft_wal_cursor as numpy records (24
+# bytes each, no padding), the fields of raft_wal_info, a fresh cursor
+WAL_HARDSTATE, WAL_TRUNCATE, WAL_ENTRY = 0, 1, 2
+WAL_KIND_NAMES = ["HARDSTATE", "TRUNCATE", "ENTRY"]
+WAL_RECORD_DTYPE = np.dtype([("group", np.int32), ("replica", np.int16), ("kind", np.int16), ("index", np.int32),
+                             ("term", np.int32), ("cmd", np.uint32), ("aux", np.int32)])
+WAL_CURSOR_DTYPE = np.dtype([("term", np.int32), ("vote", np.int32), ("stable", np.int32), ("stable_term", np.int32),
+                             ("floor", np.int32), ("pad", np.int32)])
+WAL_INFO_FIELDS = ("delivered", "pending", "hardstates", "truncates", "entries", "lost", "regressed")
+WAL_FRESH = (0, -1, 0, 0, 0, 0)
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -634,6 +660,14 @@ def load_library(path: str | None = None):
         "raft_monitor_set_availability": (C.c_int, [C.c_void_p, P(raft_monitor_availability)]),
         "raft_monitor_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
         "raft_monitor_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
+        "raft_wal_create": (C.c_int, [eng, P(C.c_void_p)]),
+        "raft_wal_destroy": (C.c_int, [C.c_void_p]),
+        "raft_wal_reset": (C.c_int, [C.c_void_p]),
+        "raft_wal_device_bytes": (I64, [C.c_void_p]),
+        "raft_wal_poll": (C.c_int, [C.c_void_p, I64, I64, I32, C.c_void_p, I64, P(raft_wal_info)]),
+        "raft_wal_poll_dev": (C.c_int, [C.c_void_p, I64, I64, I32, C.c_void_p, I64, P(raft_wal_info)]),
+        "raft_wal_read": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
+        "raft_wal_write": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -704,6 +738,8 @@ EXPORTED_SYMBOLS = [
     "raft_monitor_create", "raft_monitor_destroy", "raft_monitor_reset", "raft_monitor_device_bytes",
     "raft_monitor_observe", "raft_monitor_report", "raft_monitor_report_dev", "raft_monitor_get_availability",
     "raft_monitor_set_availability", "raft_monitor_read", "raft_monitor_write",
+    "raft_wal_create", "raft_wal_destroy", "raft_wal_reset", "raft_wal_device_bytes", "raft_wal_poll",
+    "raft_wal_poll_dev", "raft_wal_read", "raft_wal_write",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

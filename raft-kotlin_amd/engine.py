@@ -63,7 +63,7 @@ class RaftComm:
 
 class _GroupLedger:
     """What the handles that keep a ledger per group beside an engine share
-    (RaftAudit, RaftMonitor): the error check, the group-range and max_events
+    (RaftAudit, RaftMonitor, RaftWal): the error check, the group-range and max_events
     arguments, and closing on exit or collection.  A subclass sets _lib, _h and
     G and has close()."""
 
@@ -321,6 +321,158 @@ class RaftMonitor(_GroupLedger):
                     "raft_monitor_write")
 
 
+class RaftWal(_GroupLedger):
+    """The persistence stream of one engine (include/raft_engine.h raft_wal_*):
+    a cursor per replica in HBM of its own, and `poll`, which hands out what a
+    replica must make durable -- its hard state when it changed, a TRUNCATE
+    when what was handed out is no longer its log, and the entries it gained
+    since -- as records in (group, replica) order.  Apply them to a WalImage.
+    Made by RaftEngine.wal(); close it before its engine.  RaftEngine.reset
+    does not reach it: call reset() here."""
+
+    def __init__(self, engine: "RaftEngine"):
+        self._lib, self.engine = engine._lib, engine
+        self.R, self.G = engine.R, engine.G
+        h = C.c_void_p()
+        engine._check(self._lib.raft_wal_create(engine._h, C.byref(h)), "raft_wal_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.raft_wal_destroy(self._h)                       # (RaftEngine.close closes its wals first)
+            self._h = None
+
+    @property
+    def device_bytes(self) -> int:
+        """HBM owned by the stream (RaftEngine.device_bytes does not count it)."""
+        return int(self._lib.raft_wal_device_bytes(self._h))
+
+    def reset(self):
+        """Every cursor fresh (as created): the next poll sends everything."""
+        self._check(self._lib.raft_wal_reset(self._h), "wal reset")
+
+    def _args(self, g0, n, replica, max_records, what: str):
+        g0, n = self._range(g0, n, what)
+        if not isinstance(replica, (int, np.integer)) or isinstance(replica, bool) or not -1 <= replica < self.R:
+            raise ValueError(f"{what}: replica {replica!r} must be -1 (all) or in 0..{self.R - 1}")
+        if max_records is not None and (not isinstance(max_records, (int, np.integer)) or isinstance(max_records, bool)
+                                        or max_records < 0):
+            raise ValueError(f"{what}: max_records must be None or an integer >= 0, not {max_records!r}")
+        return g0, n, int(replica)
+
+    def _poll(self, fn, g0, n, replica, out_ptr, room, what: str) -> dict:
+        """One poll.  RAFT_EWINDOW is not raised: the call did everything else,
+        so info["status"] carries the code (info["lost"] > 0 says how many
+        entries left the log window unread)."""
+        wi = abi.raft_wal_info()
+        rc = fn(self._h, g0, n, replica, C.c_void_p(out_ptr or 0), int(room), C.byref(wi))
+        if rc != abi.RAFT_EWINDOW:
+            self._check(rc, what)
+        return {**{k: int(getattr(wi, k)) for k in abi.WAL_INFO_FIELDS}, "status": int(rc)}
+
+    def peek(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
+        """What a poll would see, storing nothing: info with delivered = 0 and
+        pending = every record of the selection."""
+        g0, n, replica = self._args(g0, n, replica, None, "peek")
+        return self._poll(self._lib.raft_wal_poll, g0, n, replica, 0, 0, "raft_wal_poll")
+
+    def poll(self, g0: int = 0, n: int | None = None, replica: int = -1, max_records: int | None = None):
+        """raft_wal_poll of groups [g0, g0 + n) (replica -1: every replica, else
+        that replica index): (records, info).  records is a numpy array of
+        abi.WAL_RECORD_DTYPE (group, replica, kind, index, term, cmd, aux) in
+        ascending (group, replica) order, HARDSTATE, TRUNCATE, then ENTRY
+        ascending inside a replica; at most max_records of them (None: as many
+        as there are -- a peek sizes the buffer).  The cursors advance past
+        what was returned.  info: delivered, pending, hardstates, truncates,
+        entries, lost, regressed, status."""
+        g0, n, replica = self._args(g0, n, replica, max_records, "poll")
+        if max_records is None:
+            max_records = self.peek(g0, n, replica)["pending"]
+        # room 0 with a buffer is a poll (the floors move), not a peek: never a null buffer
+        out = np.zeros(max(1, int(max_records)), dtype=abi.WAL_RECORD_DTYPE)
+        info = self._poll(self._lib.raft_wal_poll, g0, n, replica, out.ctypes.data, int(max_records), "raft_wal_poll")
+        return out[: info["delivered"]], info
+
+    def poll_dev(self, out_ptr: int, max_records: int, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
+        """poll into a DEVICE buffer of max_records 24-byte records (8-byte
+        aligned); returns the info once the kernels finished."""
+        g0, n, replica = self._args(g0, n, replica, max_records, "poll_dev")
+        if max_records is None or (max_records > 0 and not out_ptr):
+            raise ValueError("poll_dev: a device buffer and its max_records are required")
+        if out_ptr % 8:
+            raise ValueError("poll_dev: the record buffer must be 8-byte aligned")
+        return self._poll(self._lib.raft_wal_poll_dev, g0, n, replica, out_ptr, max_records, "raft_wal_poll_dev")
+
+    def cursors(self, g0: int = 0, n: int | None = None) -> np.ndarray:
+        """The cursors of groups [g0, g0 + n): [n, R] of abi.WAL_CURSOR_DTYPE
+        (term, vote, stable, stable_term, floor, pad)."""
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(int(n), 0), self.R), dtype=abi.WAL_CURSOR_DTYPE)   # a bad range is the library's to refuse
+        self._check(self._lib.raft_wal_read(self._h, int(g0), int(n), C.c_void_p(out.ctypes.data)), "raft_wal_read")
+        return out
+
+    def set_cursors(self, cursors: np.ndarray, g0: int = 0):
+        """Store the cursors of groups [g0, g0 + len(cursors)) (resuming a
+        consumer): an [n, R] array of abi.WAL_CURSOR_DTYPE.  The library refuses
+        a stable outside 0..log_cap, a floor outside 0..stable, a vote outside
+        -1..R (a node id: replica index + 1), a negative term and a nonzero pad,
+        and stores nothing then."""
+        a = np.asarray(cursors)
+        if a.ndim != 2 or a.shape[1] != self.R or a.dtype != abi.WAL_CURSOR_DTYPE:
+            raise ValueError(f"set_cursors: cursors {a.shape} {a.dtype} must be abi.WAL_CURSOR_DTYPE of shape (n, {self.R})")
+        a = np.ascontiguousarray(a)
+        self._check(self._lib.raft_wal_write(self._h, int(g0), a.shape[0], C.c_void_p(a.ctypes.data)), "raft_wal_write")
+
+
+class WalImage:
+    """What a host keeps on disk: the image the records of RaftWal.poll build,
+    in numpy only -- term [G, R], vote [G, R], length [G, R] and the entries
+    terms / cmds [G, R, cap].  apply() refuses an ENTRY that is not at
+    `length` and a TRUNCATE above `length`: a stream with a record missing or
+    out of order fails loudly instead of building a wrong image.  With
+    ring=True (an engine with a log_window) an ENTRY above `length` is
+    accepted: the entries between left the window unpersisted (the poll
+    counted them in `lost`) and stay zero in the image."""
+
+    def __init__(self, G: int, R: int, cap: int, ring: bool = False):
+        self.G, self.R, self.cap, self.ring = int(G), int(R), int(cap), bool(ring)
+        self.term = np.zeros((G, R), np.int32)
+        self.vote = np.full((G, R), -1, np.int32)
+        self.length = np.zeros((G, R), np.int32)
+        self.terms = np.zeros((G, R, cap), np.int32)
+        self.cmds = np.zeros((G, R, cap), np.uint32)
+
+    def apply(self, records: np.ndarray) -> int:
+        """Apply records (abi.WAL_RECORD_DTYPE) in order; returns how many.
+        Raises ValueError at the first record that does not fit the image,
+        with the records before it applied."""
+        rec = np.asarray(records)
+        for m, (g, r, kind, index, term, cmd, aux) in enumerate(rec.tolist()):
+            if not (0 <= g < self.G and 0 <= r < self.R):
+                raise ValueError(f"record {m}: replica ({g}, {r}) outside the image")
+            n = int(self.length[g, r])
+            if kind == abi.WAL_HARDSTATE:
+                self.term[g, r], self.vote[g, r] = term, aux
+            elif kind == abi.WAL_TRUNCATE:
+                if not 0 <= index <= n:
+                    raise ValueError(f"record {m}: TRUNCATE({index}) of ({g}, {r}) above its length {n}")
+                self.length[g, r] = index
+            elif kind == abi.WAL_ENTRY:
+                if not (index == n or (self.ring and n < index)) or index >= self.cap:
+                    raise ValueError(f"record {m}: ENTRY {index} of ({g}, {r}) is not at its length {n}")
+                self.terms[g, r, n:index], self.cmds[g, r, n:index] = 0, 0
+                self.terms[g, r, index], self.cmds[g, r, index] = term, cmd
+                self.length[g, r] = index + 1
+            else:
+                raise ValueError(f"record {m}: unknown kind {kind}")
+        return len(rec)
+
+    def log(self, g: int, r: int):
+        """(terms, cmds) of replica r of group g: its persisted entries [0, length)."""
+        n = int(self.length[g, r])
+        return self.terms[g, r, :n].copy(), self.cmds[g, r, :n].copy()
+
+
 class RaftEngine:
     def __init__(self, params: abi.raft_params, device: int = 0):
         self._lib = abi.load_library()
@@ -343,7 +495,8 @@ class RaftEngine:
 
     def close(self):
         if getattr(self, "_h", None):
-            for ref in (*getattr(self, "_audits", ()), *getattr(self, "_monitors", ())):   # they go before their engine
+            for ref in (*getattr(self, "_audits", ()), *getattr(self, "_monitors", ()),   # they go before their engine
+                        *getattr(self, "_wals", ())):
                 a = ref()
                 if a is not None:
                     a.close()
@@ -1180,6 +1333,18 @@ class RaftEngine:
             self._monitors = []
         self._monitors.append(weakref.ref(m))
         return m
+
+    # -- the persistence stream (raft_wal_*) ------------------------------------------------------------
+    def wal(self) -> RaftWal:
+        """A new persistence stream of this engine, every cursor fresh (RaftWal:
+        poll, poll_dev, peek, cursors, set_cursors, reset, device_bytes, close):
+        the first poll hands out every replica's hard state and whole log, the
+        later ones what changed.  Closing the engine closes its streams first."""
+        w = RaftWal(self)
+        if not hasattr(self, "_wals"):
+            self._wals = []
+        self._wals.append(weakref.ref(w))
+        return w
 
     # -- the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*) ---------------------------------
     def outbox_configure(self, capacity: int, expire_steps: int = 0):

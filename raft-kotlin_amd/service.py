@@ -41,6 +41,10 @@ argument meaning and error behaviour:
   liveness monitor -- which groups have no leader, a stalled commit or a
   lagging replica now and since when, and the no-ops and snapshot installs
   aimed at exactly those
+* ``RaftService.persist`` / ``recover``: the engine's persistence stream -- the
+  hard state and the log entries that changed since the last call, applied to
+  a host-side image of every node's disk (etcd's HardState and Entries in a
+  Ready), and a node given back what it had persisted after it lost it
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -57,7 +61,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import abi, wire
-from .engine import RaftEngine
+from .engine import RaftEngine, WalImage
 
 
 @dataclass
@@ -372,6 +376,59 @@ class RaftService:
         mask = np.zeros(int(g.max()) - g0 + 1, dtype=np.uint8)
         np.bitwise_or.at(mask, g - g0, (1 << r).astype(np.uint8))
         return self.engine.restart(mask, g0=g0, amnesia=amnesia, replay=replay, down_steps=down_steps)
+
+    # -- persistence: what a node writes to disk before it answers (Raft paper fig. 2, "persistent state") ---
+    def persist(self, max_records: Optional[int] = None) -> dict:
+        """Bring this service's WalImage (``wal_image``, the stand-in for every
+        node's disk) up to date: RaftWal.poll of every group until nothing is
+        pending, each batch applied to the image.  Only what changed since the
+        last call crosses the bus (etcd's Ready.HardState and Ready.Entries).
+        The stream (``wal``) and the image are made at the first call.  Returns
+        the polls' totals (delivered, hardstates, truncates, entries, lost,
+        regressed); ``last_persist`` keeps them.  After RaftEngine.reset call
+        ``wal.reset()`` and drop ``wal_image``."""
+        e = self.engine
+        if getattr(self, "wal", None) is None:
+            self.wal = e.wal()
+        if getattr(self, "wal_image", None) is None:
+            self.wal_image = WalImage(e.G, e.R, e.cap, ring=int(e.p.log_window) > 0)
+        tot = {k: 0 for k in ("delivered", "hardstates", "truncates", "entries", "lost", "regressed")}
+        while True:
+            rec, info = self.wal.poll(max_records=max_records)
+            self.wal_image.apply(rec)
+            for k in tot:
+                tot[k] += info[k]
+            if not info["pending"]:
+                break
+            if not info["delivered"]:
+                raise ValueError("persist: max_records leaves no room for a record")
+        self.last_persist = tot
+        return tot
+
+    def recover(self, group: int, replica: int) -> dict:
+        """Give node `replica` of `group` back what it had persisted (the image
+        as of the last persist()): currentTerm, votedFor and its log, with
+        lastIndex and the physical length set to the image's length -- what a
+        node with a disk reads at startup, e.g. after restart(amnesia=True) took
+        it all.  Its volatile state (role, commitIndex, timers, sessions) stays
+        as the restart left it.  One group's read_state / write_state /
+        write_log; returns {"term", "vote", "length"}."""
+        if getattr(self, "wal_image", None) is None:
+            raise ValueError("recover: nothing was persisted (persist() first)")
+        e, im = self.engine, self.wal_image
+        if not (0 <= group < e.G and 0 <= replica < e.R):
+            raise IndexError((group, replica))
+        n = int(im.length[group, replica])
+        st = e.read_state(group, 1)
+        t, c = e.read_log(group, 1)
+        t[0, replica], c[0, replica] = im.terms[group, replica], im.cmds[group, replica]
+        t[0, replica, n:], c[0, replica, n:] = 0, 0
+        base = replica * abi.NUM_FIELDS
+        for name, v in (("term", im.term[group, replica]), ("voted", im.vote[group, replica]), ("last", n), ("phys", n)):
+            st[0, base + abi.F_INDEX[name]] = int(v)
+        e.write_log(t, c, group)
+        e.write_state(st, group)
+        return {"term": int(im.term[group, replica]), "vote": int(im.vote[group, replica]), "length": n}
 
     # -- leadership transfer (Raft thesis §3.10; the reference's leader only loses leadership by timeout) ---
     def transfer_leadership(self, group: int, to: Optional[int] = None) -> str:
