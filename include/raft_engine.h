@@ -54,7 +54,9 @@ extern "C" {
  * raft_engine_sm_set_noop), the leader watch (raft_engine_poll_leaders*,
  * raft_engine_read_watch / write_watch), the proposal outbox
  * (raft_engine_outbox_*, raft_outbox_submit*), the safety audit
- * (raft_audit_*) and the liveness monitor (raft_monitor_*) */
+ * (raft_audit_*), the liveness monitor (raft_monitor_*), the persistence
+ * stream (raft_wal_*) and scripted network faults (raft_isolate_batch*,
+ * raft_engine_heal_network*, raft_engine_list_isolated*) */
 #define RAFT_ABI_VERSION 2
 
 /* ---- status codes ---------------------------------------------------- */
@@ -1757,6 +1759,121 @@ int raft_wal_poll_dev(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_
                       int64_t max_records, raft_wal_info* info);
 int raft_wal_read (raft_wal* w, int64_t g0, int64_t n, raft_wal_cursor* cursors);
 int raft_wal_write(raft_wal* w, int64_t g0, int64_t n, const raft_wal_cursor* cursors);
+
+/* ---- scripted network faults: isolate chosen replicas, heal, list ---------------
+ * Additive to ABI 2 (RAFT_ABI_VERSION stays 2: nothing that existed changed).
+ *
+ * The network faults of raft_engine_create are rates (drop_ppm, churn_ppm,
+ * partition_period).  These calls aim the one fault the engine keeps a word
+ * for: a group's isolation word, rem << 8 | replica (word 0 of the group's
+ * RAFT_GROUP_EXTRA in the canonical state), which cuts every message to and
+ * from that replica while it runs.  It is the word the churn harness sets for
+ * the lowest LEADER, raft_engine_restart sets for down_steps and
+ * raft_transfer_batch reads (RAFT_TRANSFER_UNREACHABLE); the step kernel, the
+ * digest and the canonical state are as before, and an engine that never calls
+ * these behaves as before, byte for byte.  The isolated replica keeps its state
+ * and its timers run: a cut-off leader goes on calling itself LEADER (what
+ * raft_engine_sm_get then answers from, and raft_read_begin_batch does not).
+ *
+ * - A word is RUNNING when rem > 0.  At the start of every step a running word
+ *   counts down by one and, while rem is still above 0, cuts the replica for
+ *   that step; at rem == 0 the whole word becomes 0.  So a word set to `steps`
+ *   between two steps cuts the next steps - 1 steps and is gone after `steps`
+ *   (raft_engine_restart's down_steps counts the same way).
+ * - There is one word per group: at most one replica of a group is isolated at
+ *   a time, by whoever wrote last (these calls, down_steps, the churn harness,
+ *   raft_engine_write_state).  With churn_ppm > 0 the harness isolates only in
+ *   groups whose word has run out.  Two-way partitions cannot be scripted: the
+ *   step kernel draws them from Philox per window (RAFT_RNG_PARTITION) and keeps
+ *   no word for them.
+ *
+ * raft_isolate_batch: one message per entry, "isolate target[m] of group[m]
+ * for steps[m]".  target 0..R-1 names a replica; RAFT_ISOLATE_NEWEST_LEADER is
+ * the LEADER of the highest currentTerm, the lowest index among equals
+ * (raft_read_begin_batch's and the watch's rule); RAFT_ISOLATE_LOWEST_LEADER is
+ * raft_leader_info.leader, the replica the churn harness would hit.  steps is in
+ * 1..RAFT_ISOLATE_MAX_STEPS.  Every message is judged against the state before
+ * the call, and per group only ONE message is judged: the one at the lowest
+ * batch position among the group's messages that are in range.  The ticket:
+ *   INVALID     target or steps out of range; nothing of the group is read and
+ *               the message takes no part in the choice above.  (-1, steps, 0)
+ *   DUPLICATE   an earlier message of the batch to the same group was judged;
+ *               prev is ITS BATCH POSITION.  (-1, steps, position)
+ *   NO_LEADER   a leader selector found no LEADER.  (-1, steps, word found)
+ *   BUSY        the word found is running and flags lacks RAFT_ISOLATE_REPLACE;
+ *               nothing is written.  (replica resolved, steps, word found)
+ *   SET         the word is now steps << 8 | replica.  (replica, steps, word found)
+ * in that order of precedence.  A group outside the engine fails the call with
+ * RAFT_ERANGE before a word or a ticket is written, as in the handler batches.
+ * RAFT_EINVAL: null engine, a null array with n > 0, n < 0 or >= 2^31, flag
+ * bits other than RAFT_ISOLATE_REPLACE, a _dev ticket buffer that is not
+ * 16-byte aligned.  n == 0 is RAFT_OK.
+ *
+ * raft_engine_heal_network: for every group of [g0, g0 + n) whose word is
+ * running and whose isolated replica r has bit r set in mask[j] (NULL: any
+ * replica), the word becomes 0 -- exactly what the step kernel's own expiry
+ * leaves -- and the replica hears and is heard from the next step on.  info
+ * counts the groups healed, idle (no running word; nothing is written, a stale
+ * replica byte included) and kept (running, not selected).
+ *
+ * raft_engine_list_isolated: the groups of [g0, g0 + n) with a running word as
+ * raft_isolated records in ascending group order, at most max_events of them;
+ * `running` counts them all and `pending` those left out.  out == NULL with
+ * max_events == 0 is a peek.  Read-only.  role is the isolated replica's role
+ * now (-1 if a written word names a replica outside the group).
+ *
+ * RAFT_EINVAL for heal and list: null engine or info, max_events < 0, out ==
+ * NULL with max_events > 0, a _dev record buffer that is not 16-byte aligned;
+ * RAFT_ERANGE: groups outside the engine.  n == 0 is RAFT_OK with a zeroed info.
+ *
+ * Ordering is raft_engine_drain_committed's: every call runs on the engine
+ * stream, sees every step enqueued before it, later step launches wait for it,
+ * and it returns when its kernels have finished.  The _dev forms take DEVICE
+ * pointers under the buffer rules of raft_*_batch_dev (info stays a host
+ * pointer). */
+#define RAFT_ISOLATE_NEWEST_LEADER (-1)  /* target: the LEADER of the highest currentTerm */
+#define RAFT_ISOLATE_LOWEST_LEADER (-2)  /* target: the lowest replica index whose role is LEADER */
+#define RAFT_ISOLATE_REPLACE        1    /* flags: overwrite a running isolation instead of answering BUSY */
+#define RAFT_ISOLATE_MAX_STEPS      0x7FFFFF  /* 2^23 - 1, raft_engine_restart's largest down_steps */
+#define RAFT_ISOLATE_SET            0
+#define RAFT_ISOLATE_BUSY           1
+#define RAFT_ISOLATE_NO_LEADER      2
+#define RAFT_ISOLATE_DUPLICATE      3
+#define RAFT_ISOLATE_INVALID        4
+typedef struct raft_isolate_ticket {   /* 16 bytes */
+    int32_t replica;  /* the replica named or resolved (-1: none) */
+    int32_t steps;    /* as given */
+    int32_t status;   /* RAFT_ISOLATE_SET ... RAFT_ISOLATE_INVALID */
+    int32_t prev;     /* the isolation word found; DUPLICATE: the judged message's batch position; INVALID: 0 */
+} raft_isolate_ticket;
+int raft_isolate_batch    (raft_engine* e, const int64_t* group, const int32_t* target, const int32_t* steps,
+                           int32_t flags, raft_isolate_ticket* ticket, int64_t n);
+int raft_isolate_batch_dev(raft_engine* e, const int64_t* group, const int32_t* target, const int32_t* steps,
+                           int32_t flags, raft_isolate_ticket* ticket, int64_t n);
+typedef struct raft_heal_info {        /* 32 bytes */
+    int64_t healed;       /* groups whose running word was cleared */
+    int64_t idle;         /* groups with no running word */
+    int64_t kept;         /* groups whose running word names a replica outside the mask */
+    int64_t reserved;     /* 0 */
+} raft_heal_info;
+int raft_engine_heal_network    (raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_host, raft_heal_info* info);
+int raft_engine_heal_network_dev(raft_engine* e, int64_t g0, int64_t n, const uint8_t* mask_dev, raft_heal_info* info);
+typedef struct raft_isolated {         /* 16 bytes */
+    int64_t group;        /* engine-local group index */
+    int16_t replica;      /* the isolated replica */
+    int16_t role;         /* its role now (RAFT_FOLLOWER / RAFT_CANDIDATE / RAFT_LEADER) */
+    int32_t remaining;    /* rem of the word: it cuts the next remaining - 1 steps */
+} raft_isolated;
+typedef struct raft_isolated_info {    /* 32 bytes */
+    int64_t delivered;    /* records written to out */
+    int64_t pending;      /* running - delivered */
+    int64_t running;      /* groups of the range with a running word */
+    int64_t reserved;     /* 0 */
+} raft_isolated_info;
+int raft_engine_list_isolated    (raft_engine* e, int64_t g0, int64_t n, raft_isolated* out_host, int64_t max_events,
+                                  raft_isolated_info* info);
+int raft_engine_list_isolated_dev(raft_engine* e, int64_t g0, int64_t n, raft_isolated* out_dev, int64_t max_events,
+                                  raft_isolated_info* info);
 
 /* ---- single-handler batches: the service boundary ----------------------
  * group: engine-local group index; dst: replica index 0..R-1.  Messages

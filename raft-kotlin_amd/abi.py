@@ -456,6 +456,36 @@ WAL_INFO_FIELDS = ("delivered", "pending", "hardstates", "truncates", "entries",
 WAL_FRESH = (0, -1, 0, 0, 0, 0)
 
 
+class raft_isolate_ticket(C.Structure):
+    _fields_ = [("replica", C.c_int32), ("steps", C.c_int32), ("status", C.c_int32), ("prev", C.c_int32)]
+
+
+class raft_heal_info(C.Structure):
+    _fields_ = [("healed", C.c_int64), ("idle", C.c_int64), ("kept", C.c_int64), ("reserved", C.c_int64)]
+
+
+class raft_isolated(C.Structure):
+    _fields_ = [("group", C.c_int64), ("replica", C.c_int16), ("role", C.c_int16), ("remaining", C.c_int32)]
+
+
+class raft_isolated_info(C.Structure):
+    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("running", C.c_int64), ("reserved", C.c_int64)]
+
+
+# scripted network faults (raft_isolate_batch*, raft_engine_heal_network*, raft_engine_list_isolated*): the leader
+# selectors of a target, the flag, the largest steps, raft_isolate_ticket.status, the ticket and raft_isolated as
+# numpy records (16 bytes each, no padding), the fields of the two infos
+ISOLATE_NEWEST_LEADER, ISOLATE_LOWEST_LEADER = -1, -2
+ISOLATE_REPLACE = 1
+ISOLATE_MAX_STEPS = (1 << 23) - 1
+ISOLATE_SET, ISOLATE_BUSY, ISOLATE_NO_LEADER, ISOLATE_DUPLICATE, ISOLATE_INVALID = range(5)
+ISOLATE_STATUS_NAMES = ["SET", "BUSY", "NO_LEADER", "DUPLICATE", "INVALID"]
+ISOLATE_TICKET_DTYPE = np.dtype([("replica", np.int32), ("steps", np.int32), ("status", np.int32), ("prev", np.int32)])
+ISOLATED_DTYPE = np.dtype([("group", np.int64), ("replica", np.int16), ("role", np.int16), ("remaining", np.int32)])
+HEAL_INFO_FIELDS = ("healed", "idle", "kept")
+ISOLATED_INFO_FIELDS = ("delivered", "pending", "running")
+
+
 # the reference's hard-coded constants
 DEFAULTS = dict(
     heartbeat_ms=2000,        # RaftServer.kt:115
@@ -668,6 +698,12 @@ def load_library(path: str | None = None):
         "raft_wal_poll_dev": (C.c_int, [C.c_void_p, I64, I64, I32, C.c_void_p, I64, P(raft_wal_info)]),
         "raft_wal_read": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
         "raft_wal_write": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
+        "raft_isolate_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I32, C.c_void_p, I64]),
+        "raft_isolate_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I32, C.c_void_p, I64]),
+        "raft_engine_heal_network": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_heal_info)]),
+        "raft_engine_heal_network_dev": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_heal_info)]),
+        "raft_engine_list_isolated": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_isolated_info)]),
+        "raft_engine_list_isolated_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_isolated_info)]),
         "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
         "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
         "raft_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -740,6 +776,8 @@ EXPORTED_SYMBOLS = [
     "raft_monitor_set_availability", "raft_monitor_read", "raft_monitor_write",
     "raft_wal_create", "raft_wal_destroy", "raft_wal_reset", "raft_wal_device_bytes", "raft_wal_poll",
     "raft_wal_poll_dev", "raft_wal_read", "raft_wal_write",
+    "raft_isolate_batch", "raft_isolate_batch_dev", "raft_engine_heal_network", "raft_engine_heal_network_dev",
+    "raft_engine_list_isolated", "raft_engine_list_isolated_dev",
     "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
     "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
     "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",

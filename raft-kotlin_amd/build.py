@@ -36,6 +36,7 @@ SRCS = [SRC, os.path.join(CSRC, "raft_batch.hip"),                   # the handl
         os.path.join(CSRC, "raft_audit.hip"),                        # the safety audit (invariants checked over time)
         os.path.join(CSRC, "raft_monitor.hip"),                      # the liveness monitor (outages, stalls, lag over time)
         os.path.join(CSRC, "raft_wal.hip"),                          # the persistence stream (hard state, log deltas)
+        os.path.join(CSRC, "raft_nemesis.hip"),                      # scripted network faults (isolate, heal, list)
         os.path.join(CSRC, "raft_wire.cpp"),                         # the wire codec is host code
         os.path.join(CSRC, "raft_host.cpp"),                         # page-locked batch memory
         os.path.join(CSRC, "raft_comm.cpp")]                         # the RCCL counter all-reduce (dlopen)

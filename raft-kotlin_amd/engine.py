@@ -1174,6 +1174,117 @@ class RaftEngine:
                     "raft_engine_evacuate_dev")
         return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
 
+    # -- scripted network faults (raft_isolate_batch*, raft_engine_heal_network*, raft_engine_list_isolated*) ----
+    def isolate(self, groups, targets, steps, replace: bool = False) -> np.ndarray:
+        """raft_isolate_batch: cut replica targets[m] of groups[m] off from its
+        group for steps[m] (the group's isolation word becomes steps << 8 |
+        replica: it cuts the next steps - 1 steps).  A target is a replica
+        index, abi.ISOLATE_NEWEST_LEADER or abi.ISOLATE_LOWEST_LEADER; targets
+        and steps may be scalars.  Per group only the first message of the
+        batch is judged; a running isolation is kept (BUSY) unless
+        replace=True.  Returns abi.ISOLATE_TICKET_DTYPE tickets (replica, steps,
+        status = abi.ISOLATE_SET ... ISOLATE_INVALID, prev: the word found, or
+        for DUPLICATE the judged message's position)."""
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        if g.ndim != 1:
+            raise ValueError(f"isolate: groups {g.shape} must be 1-D")
+        t, s = np.asarray(targets), np.asarray(steps)
+        for name, a in (("targets", t), ("steps", s)):
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != g.shape) or (
+                    a.size and (a.dtype.kind not in "iu" or a.min() < -0x80000000 or a.max() > 0x7FFFFFFF)):
+                raise ValueError(f"isolate: {name} must be an int32 scalar or one per group, not {a.shape} {a.dtype}")
+        t = np.ascontiguousarray(np.broadcast_to(t, g.shape), dtype=np.int32)
+        s = np.ascontiguousarray(np.broadcast_to(s, g.shape), dtype=np.int32)
+        tk = np.zeros(g.shape[0], dtype=abi.ISOLATE_TICKET_DTYPE)
+        self._check(self._lib.raft_isolate_batch(
+            self._h, C.c_void_p(g.ctypes.data), C.c_void_p(t.ctypes.data), C.c_void_p(s.ctypes.data),
+            abi.ISOLATE_REPLACE if replace else 0, C.c_void_p(tk.ctypes.data), g.shape[0]), "raft_isolate_batch")
+        return tk
+
+    def isolate_dev(self, group_ptr: int, target_ptr: int, steps_ptr: int, ticket_ptr: int, n: int,
+                    replace: bool = False, after_stream: int | None = None) -> int:
+        """raft_isolate_batch_dev: DEVICE pointers to n int64 groups, int32
+        targets, int32 steps and 16-byte tickets (16-byte aligned), e.g. torch
+        tensors' data_ptr(); returns RAFT_OK once the batch finished."""
+        if ticket_ptr % 16:
+            raise ValueError("isolate_dev: the ticket buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._client_status(self._lib.raft_isolate_batch_dev(
+            self._h, group_ptr, target_ptr, steps_ptr, abi.ISOLATE_REPLACE if replace else 0, ticket_ptr, int(n)),
+            "raft_isolate_batch_dev", ())
+
+    def heal_network(self, mask=None, g0: int = 0, n: int | None = None) -> dict:
+        """raft_engine_heal_network: clear the running isolation word of every
+        group of [g0, g0 + n) whose isolated replica r has bit r set in mask[j]
+        (mask=None: whichever replica it is) -- the state the step kernel's own
+        expiry leaves.  Returns healed, idle (nothing was running), kept
+        (running, not selected)."""
+        m = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
+                raise ValueError(f"heal_network: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
+            n = m.shape[0] if n is None else n
+            if m.shape[0] != n:
+                raise ValueError(f"heal_network: mask holds {m.shape[0]} groups, n is {n}")
+            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
+        n = self.G - g0 if n is None else n
+        for name, v in (("g0", g0), ("n", n)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"heal_network: {name} must be an integer, not {v!r}")
+        hi = abi.raft_heal_info()
+        self._check(self._lib.raft_engine_heal_network(self._h, int(g0), int(n),
+                                                       C.c_void_p(m.ctypes.data) if m is not None and m.size else None,
+                                                       C.byref(hi)), "raft_engine_heal_network")
+        return {k: int(getattr(hi, k)) for k in abi.HEAL_INFO_FIELDS}
+
+    def heal_network_dev(self, mask_ptr: int, n: int, g0: int = 0, after_stream: int | None = None) -> dict:
+        """heal_network with the mask in DEVICE memory (n bytes on this engine's
+        GPU, e.g. a torch uint8 tensor's data_ptr(); 0: any replica); returns
+        once the kernel finished."""
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        hi = abi.raft_heal_info()
+        self._check(self._lib.raft_engine_heal_network_dev(self._h, int(g0), int(n), C.c_void_p(mask_ptr or 0),
+                                                           C.byref(hi)), "raft_engine_heal_network_dev")
+        return {k: int(getattr(hi, k)) for k in abi.HEAL_INFO_FIELDS}
+
+    def _list_isolated(self, fn, g0, n, out_ptr, room, what: str) -> dict:
+        ii = abi.raft_isolated_info()
+        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(ii)), what)
+        return {k: int(getattr(ii, k)) for k in abi.ISOLATED_INFO_FIELDS}
+
+    def isolated(self, g0: int = 0, n: int | None = None, max_events: int | None = None, peek: bool = False):
+        """raft_engine_list_isolated: the groups of [g0, g0 + n) with a running
+        isolation: (info, records).  records is a numpy array of
+        abi.ISOLATED_DTYPE (group, replica, role of that replica now, remaining)
+        in ascending group order, at most max_events of them (None: as many as
+        there are).  peek=True returns no record.  info: delivered, pending,
+        running.  Read-only."""
+        g0, n = self._watch_args(g0, n, max_events, "isolated")
+        fn = self._lib.raft_engine_list_isolated
+        if peek:
+            return self._list_isolated(fn, g0, n, 0, 0, "isolated"), np.zeros(0, dtype=abi.ISOLATED_DTYPE)
+        if max_events is None:
+            max_events = self._list_isolated(fn, g0, n, 0, 0, "isolated")["pending"]
+        out = np.zeros(max(1, int(max_events)), dtype=abi.ISOLATED_DTYPE)   # never a null buffer: that would be a peek
+        info = self._list_isolated(fn, g0, n, out.ctypes.data, int(max_events), "isolated")
+        return info, out[: info["delivered"]]
+
+    def isolated_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None,
+                     after_stream: int | None = None) -> dict:
+        """isolated into a DEVICE buffer of max_events 16-byte records (16-byte
+        aligned); returns the info once the kernels finished."""
+        g0, n = self._watch_args(g0, n, max_events, "isolated_dev")
+        if max_events is None or (max_events > 0 and not out_ptr):
+            raise ValueError("isolated_dev: a device buffer and its max_events are required")
+        if out_ptr % 16:
+            raise ValueError("isolated_dev: the record buffer must be 16-byte aligned")
+        if after_stream is not None:
+            self.wait_stream(after_stream)
+        return self._list_isolated(self._lib.raft_engine_list_isolated_dev, g0, n, out_ptr, max_events, "isolated_dev")
+
     # -- leader no-op entries (raft_engine_append_noops*, raft_engine_sm_set_noop) -------------------------
     def _noop_args(self, g0, n, cmd, what: str):
         n = self.G - g0 if n is None else n

@@ -187,8 +187,19 @@ class RaftNode:
     def restart(self, amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
         """Kill this node's process and launch it again (main, RaftServer.kt:302-310).
         amnesia=True is what the reference does, since it persists nothing:
-        entries() is empty and currentTerm is 0 afterwards."""
+        entries() is empty and currentTerm is 0 afterwards.  down_steps cuts
+        the restarted node off for that long; to cut a node off WITHOUT
+        restarting it (its state kept, its timers running) use isolate()."""
         return self.s.restart([self.group], [self.replica], amnesia=amnesia, replay=replay, down_steps=down_steps)
+
+    def isolate(self, steps: int, replace: bool = False) -> str:
+        """Unplug this node's network cable for `steps` (RaftService.isolate):
+        nothing it sends arrives and nothing reaches it, its state stays and
+        its timers run -- a leader goes on calling itself LEADER.  Returns the
+        ticket's status name ("SET", or "BUSY" when another isolation of the
+        group is running and replace is False)."""
+        tk = self.s.isolate([self.group], [self.replica], steps, replace=replace)
+        return abi.ISOLATE_STATUS_NAMES[int(tk["status"][0])]
 
     def install(self, min_lag: int = 0) -> dict:
         """Bring this node up to its group's newest leader (RaftEngine.install_snapshot
@@ -363,7 +374,9 @@ class RaftService:
     def restart(self, groups, replicas, amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
         """Restart node replicas[m] of groups[m], all in one device call (a
         node named twice restarts once): the mask of RaftEngine.restart over
-        the span of the named groups.  Returns its info."""
+        the span of the named groups.  Returns its info.  down_steps isolates
+        the lowest restarted node of each group; isolate() cuts a node off
+        without restarting it."""
         g = np.asarray(groups, dtype=np.int64).reshape(-1)
         r = np.asarray(replicas, dtype=np.int64).reshape(-1)
         if g.shape != r.shape:
@@ -376,6 +389,41 @@ class RaftService:
         mask = np.zeros(int(g.max()) - g0 + 1, dtype=np.uint8)
         np.bitwise_or.at(mask, g - g0, (1 << r).astype(np.uint8))
         return self.engine.restart(mask, g0=g0, amnesia=amnesia, replay=replay, down_steps=down_steps)
+
+    # -- scripted network faults: a node's cable pulled and put back (the reference has no counterpart) ---
+    def isolate(self, groups, replicas, steps, replace: bool = False) -> np.ndarray:
+        """Cut node replicas[m] of groups[m] off from its group for `steps`
+        (RaftEngine.isolate: one device call, one isolated node per group, per
+        group the first message counts).  replicas="leader" names each group's
+        newest leader -- the one a linearizable read asks -- and
+        "lowest_leader" the one RaftService.leader returns.  Returns the
+        tickets; ``last_isolate`` keeps them."""
+        sel = {"leader": abi.ISOLATE_NEWEST_LEADER, "lowest_leader": abi.ISOLATE_LOWEST_LEADER}
+        if isinstance(replicas, str):
+            if replicas not in sel:
+                raise ValueError(f"isolate: replicas must be node indices, 'leader' or 'lowest_leader', not {replicas!r}")
+            replicas = sel[replicas]
+        else:
+            replicas = np.asarray(replicas)
+            if replicas.size and (replicas.min() < 0 or replicas.max() >= self.engine.R):
+                raise IndexError("isolate: a node outside the engine")
+        self.last_isolate = self.engine.isolate(np.asarray(groups, dtype=np.int64).reshape(-1), replicas, steps,
+                                                replace=replace)
+        return self.last_isolate
+
+    def heal_network(self) -> dict:
+        """Put every pulled cable back (RaftEngine.heal_network over every group):
+        healed, idle, kept.  A healed stale leader steps down when it hears of
+        the new term, a step or a heartbeat later."""
+        return self.engine.heal_network()
+
+    def isolated(self) -> List[tuple]:
+        """The nodes cut off right now as (RaftNode, its state name, steps
+        remaining), in group order (RaftEngine.isolated)."""
+        _, rec = self.engine.isolated()
+        names = ("FOLLOWER", "CANDIDATE", "LEADER")
+        return [(RaftNode(self, int(g), int(r)), names[role] if 0 <= role < 3 else "?", int(rem))
+                for g, r, role, rem in rec.tolist()]
 
     # -- persistence: what a node writes to disk before it answers (Raft paper fig. 2, "persistent state") ---
     def persist(self, max_records: Optional[int] = None) -> dict:
@@ -445,7 +493,9 @@ class RaftService:
         while the leader directory (RaftEngine.leaders) names it in some group
         and the budget lasts, one evacuate of that replica over every group and
         one step.  Returns how many groups it still leads; ``last_drain`` keeps
-        the turns taken and each turn's evacuate info."""
+        the turns taken and each turn's evacuate info.  A node that isolate()
+        (or a restart's down_steps) has cut off is UNREACHABLE as a target and
+        counts under an evacuate's busy."""
         e = self.engine
         if not 0 <= replica < e.R:
             raise IndexError(replica)
