@@ -4,6 +4,10 @@ Pure data definitions: structs, constants, and the loader of the HIP engine
 library.  The loader never falls back to anything: if the in-tree
 ``lib/libraft_engine.so`` is missing it raises, so a GPU run cannot silently
 take another path.
+
+Every record is declared once, with `record`; its numpy dtype and the tuple
+of its scalar fields come from that declaration.  Every entry point is
+declared once, in `SIGNATURES`.
 """
 from __future__ import annotations
 
@@ -127,21 +131,40 @@ def group_words(R: int) -> int:
     return R * NUM_FIELDS + 2 * R * R + GROUP_EXTRA
 
 
-class raft_params(C.Structure):
-    _fields_ = [
-        ("R", C.c_int32), ("log_cap", C.c_int32), ("G", C.c_int64), ("g0", C.c_int64),
-        ("seed", C.c_uint64),
-        ("heartbeat_ms", C.c_int32), ("election_min_ms", C.c_int32), ("election_max_ms", C.c_int32),
-        ("backoff_min_ms", C.c_int32), ("backoff_max_ms", C.c_int32),
-        ("round_timeout_ms", C.c_int32), ("retry_ms", C.c_int32),
-        ("drop_ppm", C.c_uint32), ("churn_ppm", C.c_uint32), ("churn_steps", C.c_int32),
-        ("partition_period", C.c_int32), ("partition_len", C.c_int32),
-        ("cmd_ppm", C.c_uint32), ("cmd_mode", C.c_int32), ("cmd_limit", C.c_int32),
-        ("steps_per_launch", C.c_int32), ("mode", C.c_int32), ("log_window", C.c_int32),
-        ("ae_max_entries", C.c_int32), ("subranges", C.c_int32), ("schedule", C.c_int32),
-        ("schedule_workgroups", C.c_int32), ("kernel", C.c_int32),
-    ]
+I16, I32, I64, U32, U64 = C.c_int16, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 
+
+def record(name: str, *groups):
+    """The one declaration of a C-ABI record, written like its typedef in the
+    header: `groups` are (names, ctype) pairs, names a string of field names
+    that share the type, `reserved[3]` for an array.  Returns the
+    ctypes.Structure; it carries `dtype`, the same fields as a packed numpy
+    dtype (the records that travel as arrays have no padding, so the two agree
+    on size and offsets: tests/test_abi.py holds every public *_DTYPE to
+    that), and `scalars`, the names of its fields without the
+    reserved ones and the arrays (what an info struct becomes a dict of)."""
+    fields = []
+    for names, ctype in groups:
+        for k in names.split():
+            k, _, count = k.partition("[")
+            fields.append((k, ctype * int(count[:-1]) if count else ctype))
+    return type(name, (C.Structure,), {
+        "_fields_": fields,
+        "dtype": np.dtype([(k, np.dtype(t)) for k, t in fields]),
+        "scalars": tuple(k for k, t in fields if not issubclass(t, C.Array) and not k.startswith("reserved"))})
+
+
+def info_dict(info: C.Structure, fields=None) -> dict:
+    """An info struct as a dict of ints: `fields` of it, or its scalar fields."""
+    return {k: int(getattr(info, k)) for k in (type(info).scalars if fields is None else fields)}
+
+
+raft_params = record(
+    "raft_params", ("R log_cap", I32), ("G g0", I64), ("seed", U64),
+    ("heartbeat_ms election_min_ms election_max_ms backoff_min_ms backoff_max_ms round_timeout_ms retry_ms", I32),
+    ("drop_ppm churn_ppm", U32), ("churn_steps partition_period partition_len", I32), ("cmd_ppm", U32),
+    ("cmd_mode cmd_limit steps_per_launch mode log_window ae_max_entries subranges schedule schedule_workgroups "
+     "kernel", I32))
 
 # step-kernel schedules (raft_params.schedule)
 SCHED_AUTO, SCHED_ONE_PER_WAVE, SCHED_BALANCED = 0, 1, 2
@@ -150,231 +173,122 @@ KERNEL_AUTO, KERNEL_GENERAL = 0, 1
 # raft_engine_set_batch_path
 BATCH_PATH_AUTO, BATCH_PATH_SORTED, BATCH_PATH_BUCKETED = 0, 1, 2
 
+raft_kernel_info = record("raft_kernel_info", ("net textbook ring steps workgroups resident_workgroups balanced "
+                                               "subranges reserved[4]", I32))
 
-class raft_kernel_info(C.Structure):
-    _fields_ = [("net", C.c_int32), ("textbook", C.c_int32), ("ring", C.c_int32), ("steps", C.c_int32),
-                ("workgroups", C.c_int32), ("resident_workgroups", C.c_int32), ("balanced", C.c_int32),
-                ("subranges", C.c_int32), ("reserved", C.c_int32 * 4)]
+# the service boundary's messages (raft_vote_batch*, raft_append_batch*)
+raft_vote_req = record("raft_vote_req", ("term candidate_id last_log_index last_log_term", I32))
+raft_vote_resp = record("raft_vote_resp", ("term vote_granted", I32))
+raft_append_req = record("raft_append_req", ("term leader_id prev_log_index prev_log_term has_entry entry_term", I32),
+                         ("entry_cmd", U32), ("leader_commit", I32))
+raft_append_resp = record("raft_append_resp", ("term success status", I32))
 
+# committed-entry delivery (raft_engine_drain_committed*): raft_applied_entry is 24 bytes
+raft_applied_entry = record("raft_applied_entry", ("group", I64), ("replica index term", I32), ("cmd", U32))
+raft_drain_info = record("raft_drain_info", ("delivered pending lost regressed", I64))
+APPLIED_DTYPE = raft_applied_entry.dtype
 
-class raft_vote_req(C.Structure):
-    _fields_ = [("term", C.c_int32), ("candidate_id", C.c_int32),
-                ("last_log_index", C.c_int32), ("last_log_term", C.c_int32)]
-
-
-class raft_vote_resp(C.Structure):
-    _fields_ = [("term", C.c_int32), ("vote_granted", C.c_int32)]
-
-
-class raft_append_req(C.Structure):
-    _fields_ = [("term", C.c_int32), ("leader_id", C.c_int32), ("prev_log_index", C.c_int32),
-                ("prev_log_term", C.c_int32), ("has_entry", C.c_int32), ("entry_term", C.c_int32),
-                ("entry_cmd", C.c_uint32), ("leader_commit", C.c_int32)]
-
-
-class raft_append_resp(C.Structure):
-    _fields_ = [("term", C.c_int32), ("success", C.c_int32), ("status", C.c_int32)]
-
-
-class raft_applied_entry(C.Structure):
-    _fields_ = [("group", C.c_int64), ("replica", C.c_int32), ("index", C.c_int32), ("term", C.c_int32),
-                ("cmd", C.c_uint32)]
-
-
-class raft_drain_info(C.Structure):
-    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("lost", C.c_int64), ("regressed", C.c_int64)]
-
-
-# raft_applied_entry as a numpy record (24 bytes, no padding)
-APPLIED_DTYPE = np.dtype([("group", np.int64), ("replica", np.int32), ("index", np.int32), ("term", np.int32),
-                          ("cmd", np.uint32)])
-
-
-class raft_leader_info(C.Structure):
-    _fields_ = [("leader", C.c_int32), ("term", C.c_int32), ("n_leaders", C.c_int32), ("commit", C.c_int32)]
-
-
-class raft_ticket(C.Structure):
-    _fields_ = [("replica", C.c_int32), ("index", C.c_int32), ("term", C.c_int32), ("status", C.c_int32)]
-
-
-class raft_ticket_state(C.Structure):
-    _fields_ = [("status", C.c_int32), ("holders", C.c_int32), ("committed_on", C.c_int32), ("unknown", C.c_int32)]
-
-
-# the client path's records as numpy records (16 bytes each, no padding)
-LEADER_DTYPE = np.dtype([("leader", np.int32), ("term", np.int32), ("n_leaders", np.int32), ("commit", np.int32)])
-TICKET_DTYPE = np.dtype([("replica", np.int32), ("index", np.int32), ("term", np.int32), ("status", np.int32)])
-TICKET_STATE_DTYPE = np.dtype([("status", np.int32), ("holders", np.int32), ("committed_on", np.int32),
-                               ("unknown", np.int32)])
-# raft_ticket.status (RAFT_PROPOSE_*) and raft_ticket_state.status (RAFT_TICKET_*)
+# the client path's records (16 bytes each), raft_ticket.status (RAFT_PROPOSE_*) and raft_ticket_state.status
+# (RAFT_TICKET_*)
+raft_leader_info = record("raft_leader_info", ("leader term n_leaders commit", I32))
+raft_ticket = record("raft_ticket", ("replica index term status", I32))
+raft_ticket_state = record("raft_ticket_state", ("status holders committed_on unknown", I32))
+LEADER_DTYPE = raft_leader_info.dtype
+TICKET_DTYPE = raft_ticket.dtype
+TICKET_STATE_DTYPE = raft_ticket_state.dtype
 PROPOSE_ACCEPTED, PROPOSE_GHOSTED, PROPOSE_NO_LEADER, PROPOSE_LOG_FULL = 0, 1, 2, 3
 TICKET_NONE, TICKET_COMMITTED, TICKET_PENDING, TICKET_LOST, TICKET_UNKNOWN, TICKET_INVALID = 0, 1, 2, 3, 4, 5
 TICKET_STATUS_NAMES = ["NONE", "COMMITTED", "PENDING", "LOST", "UNKNOWN", "INVALID"]
 
-
-class raft_sm_info(C.Structure):
-    _fields_ = [("applied", C.c_int64), ("lost", C.c_int64), ("regressed", C.c_int64), ("reserved", C.c_int64)]
-
-
-class raft_sm_head(C.Structure):
-    _fields_ = [("applied", C.c_int32), ("lost", C.c_int32), ("hash", C.c_uint64)]
-
-
-class raft_sm_value(C.Structure):
-    _fields_ = [("value", C.c_uint32), ("replica", C.c_int32), ("applied", C.c_int32), ("commit", C.c_int32)]
-
-
-# the state machine's records as numpy records (16 bytes each, no padding)
-SM_HEAD_DTYPE = np.dtype([("applied", np.int32), ("lost", np.int32), ("hash", np.uint64)])
-SM_VALUE_DTYPE = np.dtype([("value", np.uint32), ("replica", np.int32), ("applied", np.int32), ("commit", np.int32)])
+# the state machine's records (16 bytes each)
+raft_sm_info = record("raft_sm_info", ("applied lost regressed reserved", I64))
+raft_sm_head = record("raft_sm_head", ("applied lost", I32), ("hash", U64))
+raft_sm_value = record("raft_sm_value", ("value", U32), ("replica applied commit", I32))
+SM_HEAD_DTYPE = raft_sm_head.dtype
+SM_VALUE_DTYPE = raft_sm_value.dtype
 SM_SLOTS = (1, 2, 4, 8, 16, 32, 64)      # raft_engine_sm_configure: registers per replica
 
-
-class raft_restart_info(C.Structure):
-    _fields_ = [("restarted", C.c_int64), ("leaders", C.c_int64), ("entries_dropped", C.c_int64),
-                ("reserved", C.c_int64)]
-
-
-# raft_engine_restart*: flags, the largest down_steps, the Philox purposes (RAFT_RNG_*)
+# raft_engine_restart*: the info, the flags, the largest down_steps, the Philox purposes (RAFT_RNG_*)
+raft_restart_info = record("raft_restart_info", ("restarted leaders entries_dropped reserved", I64))
 RESTART_AMNESIA, RESTART_REPLAY = 1, 2
 RESTART_MAX_DOWN_STEPS = (1 << 23) - 1
 RNG_TIMER, RNG_RESTART = 1, 7
 
+# raft_engine_install_snapshot*: the info (64 bytes)
+raft_install_info = record("raft_install_info", ("installed slots_copied no_leader leader_gapped ahead reserved[3]", I64))
+INSTALL_INFO_DTYPE = raft_install_info.dtype
+INSTALL_INFO_FIELDS = raft_install_info.scalars
 
-class raft_install_info(C.Structure):
-    _fields_ = [("installed", C.c_int64), ("slots_copied", C.c_int64), ("no_leader", C.c_int64),
-                ("leader_gapped", C.c_int64), ("ahead", C.c_int64), ("reserved", C.c_int64 * 3)]
-
-
-# raft_engine_install_snapshot*: the info as a numpy record (64 bytes, no padding)
-INSTALL_INFO_DTYPE = np.dtype([("installed", np.int64), ("slots_copied", np.int64), ("no_leader", np.int64),
-                               ("leader_gapped", np.int64), ("ahead", np.int64), ("reserved", np.int64, (3,))])
-INSTALL_INFO_FIELDS = ("installed", "slots_copied", "no_leader", "leader_gapped", "ahead")
-
-
-class raft_read_ticket(C.Structure):
-    _fields_ = [("replica", C.c_int32), ("term", C.c_int32), ("read_index", C.c_int32), ("status", C.c_int32)]
-
-
-class raft_read_result(C.Structure):
-    _fields_ = [("value", C.c_uint32), ("status", C.c_int32), ("applied", C.c_int32), ("agree", C.c_int32)]
-
-
-# linearizable reads: the records as numpy records (16 bytes each, no padding), raft_read_ticket.status and
-# raft_read_result.status (RAFT_READ_*)
-READ_TICKET_DTYPE = np.dtype([("replica", np.int32), ("term", np.int32), ("read_index", np.int32), ("status", np.int32)])
-READ_RESULT_DTYPE = np.dtype([("value", np.uint32), ("status", np.int32), ("applied", np.int32), ("agree", np.int32)])
+# linearizable reads: the records (16 bytes each), raft_read_ticket.status and raft_read_result.status
+# (RAFT_READ_*)
+raft_read_ticket = record("raft_read_ticket", ("replica term read_index status", I32))
+raft_read_result = record("raft_read_result", ("value", U32), ("status applied agree", I32))
+READ_TICKET_DTYPE = raft_read_ticket.dtype
+READ_RESULT_DTYPE = raft_read_result.dtype
 READ_ISSUED, READ_TERM_UNCOMMITTED, READ_NO_LEADER, READ_UNKNOWN = 0, 1, 2, 3
 READ_TICKET_STATUS_NAMES = ["ISSUED", "TERM_UNCOMMITTED", "NO_LEADER", "UNKNOWN"]
 READ_SERVED, READ_BEHIND, READ_GAPPED, READ_NO_QUORUM, READ_DEPOSED, READ_NONE, READ_INVALID = 0, 1, 2, 3, 4, 5, 6
 READ_STATUS_NAMES = ["SERVED", "BEHIND", "GAPPED", "NO_QUORUM", "DEPOSED", "NONE", "INVALID"]
 
-
-class raft_transfer_ticket(C.Structure):
-    _fields_ = [("from", C.c_int32), ("term", C.c_int32), ("target", C.c_int32), ("status", C.c_int32)]
-
-
-class raft_transfer_state(C.Structure):
-    _fields_ = [("status", C.c_int32), ("leader", C.c_int32), ("term", C.c_int32), ("reserved", C.c_int32)]
-
-
-class raft_evacuate_info(C.Structure):
-    _fields_ = [("led", C.c_int64), ("sent", C.c_int64), ("no_target", C.c_int64), ("behind", C.c_int64),
-                ("busy", C.c_int64), ("reserved", C.c_int64 * 3)]
-
-
-# leadership transfer: the records as numpy records (16 bytes each, no padding), raft_transfer_ticket.status and
-# raft_transfer_state.status (RAFT_TRANSFER_*)
-TRANSFER_TICKET_DTYPE = np.dtype([("from", np.int32), ("term", np.int32), ("target", np.int32), ("status", np.int32)])
-TRANSFER_STATE_DTYPE = np.dtype([("status", np.int32), ("leader", np.int32), ("term", np.int32), ("reserved", np.int32)])
+# leadership transfer: the records (16 bytes each), raft_transfer_ticket.status and raft_transfer_state.status
+# (RAFT_TRANSFER_*)
+raft_transfer_ticket = record("raft_transfer_ticket", ("from term target status", I32))
+raft_transfer_state = record("raft_transfer_state", ("status leader term reserved", I32))
+raft_evacuate_info = record("raft_evacuate_info", ("led sent no_target behind busy reserved[3]", I64))
+TRANSFER_TICKET_DTYPE = raft_transfer_ticket.dtype
+TRANSFER_STATE_DTYPE = raft_transfer_state.dtype
 TRANSFER_AUTO = -1
 (TRANSFER_SENT, TRANSFER_NO_LEADER, TRANSFER_SELF, TRANSFER_BEHIND, TRANSFER_BUSY, TRANSFER_UNREACHABLE,
  TRANSFER_NO_TARGET, TRANSFER_INVALID) = range(8)
 TRANSFER_TICKET_STATUS_NAMES = ["SENT", "NO_LEADER", "SELF", "BEHIND", "BUSY", "UNREACHABLE", "NO_TARGET", "INVALID"]
 TRANSFER_COMPLETED, TRANSFER_PENDING, TRANSFER_SUPERSEDED, TRANSFER_NONE = 0, 1, 2, 3
 TRANSFER_STATE_NAMES = {0: "COMPLETED", 1: "PENDING", 2: "SUPERSEDED", 3: "NONE", 7: "INVALID"}
-EVACUATE_INFO_FIELDS = ("led", "sent", "no_target", "behind", "busy")
+EVACUATE_INFO_FIELDS = raft_evacuate_info.scalars
 
-
-class raft_noop_info(C.Structure):
-    _fields_ = [("appended", C.c_int64), ("current", C.c_int64), ("no_leader", C.c_int64), ("log_full", C.c_int64),
-                ("ghosted", C.c_int64), ("reserved", C.c_int64 * 3)]
-
-
-# leader no-op entries (raft_engine_append_noops*): the ticket status of a group whose leader's last entry is of
-# its own term already (RAFT_PROPOSE_CURRENT, beside PROPOSE_* above), the info as a numpy record (64 bytes, no
-# padding)
+# leader no-op entries (raft_engine_append_noops*): the info (64 bytes), the ticket status of a group whose
+# leader's last entry is of its own term already (RAFT_PROPOSE_CURRENT, beside PROPOSE_* above)
+raft_noop_info = record("raft_noop_info", ("appended current no_leader log_full ghosted reserved[3]", I64))
 PROPOSE_CURRENT = 4
 NOOP_CMD = 0                 # RaftEngine.append_noops' default command id (any u32 the caller's commands never use)
 PROPOSE_STATUS_NAMES = ["ACCEPTED", "GHOSTED", "NO_LEADER", "LOG_FULL", "CURRENT"]
-NOOP_INFO_DTYPE = np.dtype([("appended", np.int64), ("current", np.int64), ("no_leader", np.int64),
-                            ("log_full", np.int64), ("ghosted", np.int64), ("reserved", np.int64, (3,))])
-NOOP_INFO_FIELDS = ("appended", "current", "no_leader", "log_full", "ghosted")
+NOOP_INFO_DTYPE = raft_noop_info.dtype
+NOOP_INFO_FIELDS = raft_noop_info.scalars
 
-
-class raft_leader_event(C.Structure):
-    _fields_ = [("group", C.c_int64), ("leader", C.c_int32), ("term", C.c_int32), ("prev_leader", C.c_int32),
-                ("prev_term", C.c_int32)]
-
-
-class raft_watch_info(C.Structure):
-    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("gained", C.c_int64), ("lost", C.c_int64),
-                ("moved", C.c_int64), ("reterm", C.c_int64), ("leaderless", C.c_int64), ("reserved", C.c_int64)]
-
-
-# the leader watch (raft_engine_poll_leaders*): raft_leader_event as a numpy record (24 bytes, no padding), the
-# info as one (64 bytes), a `seen` pair before the first report
-EVENT_DTYPE = np.dtype([("group", np.int64), ("leader", np.int32), ("term", np.int32), ("prev_leader", np.int32),
-                        ("prev_term", np.int32)])
-WATCH_INFO_DTYPE = np.dtype([("delivered", np.int64), ("pending", np.int64), ("gained", np.int64), ("lost", np.int64),
-                             ("moved", np.int64), ("reterm", np.int64), ("leaderless", np.int64),
-                             ("reserved", np.int64)])
-WATCH_INFO_FIELDS = ("delivered", "pending", "gained", "lost", "moved", "reterm", "leaderless")
+# the leader watch (raft_engine_poll_leaders*): raft_leader_event (24 bytes), the info (64 bytes), a `seen` pair
+# before the first report
+raft_leader_event = record("raft_leader_event", ("group", I64), ("leader term prev_leader prev_term", I32))
+raft_watch_info = record("raft_watch_info", ("delivered pending gained lost moved reterm leaderless reserved", I64))
+EVENT_DTYPE = raft_leader_event.dtype
+WATCH_INFO_DTYPE = raft_watch_info.dtype
+WATCH_INFO_FIELDS = raft_watch_info.scalars
 WATCH_UNSEEN = (-1, 0)
 
-
-class raft_outbox_info(C.Structure):
-    _fields_ = [(k, C.c_int64) for k in ("queued", "committed", "expired", "deferred", "pending", "orphaned", "unknown",
-                                         "retried", "accepted", "ghosted", "no_leader", "log_full", "left")] + [
-        ("age_hist", C.c_int64 * 32)]
-
-
-# the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*): raft_outbox_entry (48 bytes) and raft_outbox_done
-# (32 bytes) as numpy records without padding, the scalar fields of raft_outbox_info, the status words
+# the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*): the info, raft_outbox_entry (48 bytes) and
+# raft_outbox_done (32 bytes) as numpy records without padding, the status words
+raft_outbox_info = record("raft_outbox_info", ("queued committed expired deferred pending orphaned unknown retried "
+                                               "accepted ghosted no_leader log_full left age_hist[32]", I64))
 OUTBOX_ENTRY_DTYPE = np.dtype([("tag", np.int64), ("born", np.int64), ("group", np.int32), ("cmd", np.uint32),
                                ("replica", np.int32), ("index", np.int32), ("term", np.int32), ("status", np.int32),
                                ("tries", np.int32), ("pad", np.int32)])
 OUTBOX_DONE_DTYPE = np.dtype([("tag", np.int64), ("group", np.int32), ("status", np.int32), ("index", np.int32),
                               ("term", np.int32), ("tries", np.int32), ("age", np.int32)])
-OUTBOX_INFO_FIELDS = ("queued", "committed", "expired", "deferred", "pending", "orphaned", "unknown", "retried",
-                      "accepted", "ghosted", "no_leader", "log_full", "left")
+OUTBOX_INFO_FIELDS = raft_outbox_info.scalars
 OUTBOX_NEW, OUTBOX_COMMITTED, OUTBOX_EXPIRED = -1, 1, 2
 OUTBOX_DONE_NAMES = {1: "COMMITTED", 2: "EXPIRED"}
 
-
-class raft_audit_info(C.Structure):
-    _fields_ = [(k, C.c_int64) for k in ("newly_flagged", "flagged", "term_regressed", "vote_changed", "two_leaders",
-                                         "commit_changed", "leader_incomplete", "unknown")]
-
-
-class raft_audit_event(C.Structure):
-    _fields_ = [("group", C.c_int64), ("flags", C.c_int32), ("first_step", C.c_int32)]
-
-
-class raft_audit_report_info(C.Structure):
-    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("flagged", C.c_int64), ("reserved", C.c_int64 * 5)]
-
-
 # the safety audit (raft_audit_*): the sticky flag bits in the order of raft_audit_info's per-kind counts,
-# raft_audit_event as a numpy record (16 bytes, no padding), the words of a group's exported ledger
+# raft_audit_event (16 bytes), the words of a group's exported ledger
+raft_audit_info = record("raft_audit_info", ("newly_flagged flagged term_regressed vote_changed two_leaders "
+                                             "commit_changed leader_incomplete unknown", I64))
+raft_audit_event = record("raft_audit_event", ("group", I64), ("flags first_step", I32))
+raft_audit_report_info = record("raft_audit_report_info", ("delivered pending flagged reserved[5]", I64))
 AUDIT_TERM_REGRESSED, AUDIT_VOTE_CHANGED, AUDIT_TWO_LEADERS, AUDIT_COMMIT_CHANGED, AUDIT_LEADER_INCOMPLETE = \
     1, 2, 4, 8, 16
-AUDIT_KINDS = ("term_regressed", "vote_changed", "two_leaders", "commit_changed", "leader_incomplete")
+AUDIT_KINDS = raft_audit_info.scalars[2:7]
 AUDIT_ALL = 31
-AUDIT_INFO_FIELDS = ("newly_flagged", "flagged") + AUDIT_KINDS + ("unknown",)
-AUDIT_REPORT_FIELDS = ("delivered", "pending", "flagged")
-AUDIT_EVENT_DTYPE = np.dtype([("group", np.int64), ("flags", np.int32), ("first_step", np.int32)])
+AUDIT_INFO_FIELDS = raft_audit_info.scalars
+AUDIT_REPORT_FIELDS = raft_audit_report_info.scalars
+AUDIT_EVENT_DTYPE = raft_audit_event.dtype
 AUDIT_WORDS = ("flags", "first_step", "lead_term", "lead_replica", "anchor_count", "anchor_term", "anchor_cmd",
                "anchor_seen_term")
 AUDIT_HEAD = len(AUDIT_WORDS)
@@ -385,43 +299,24 @@ def audit_words(R: int) -> int:
     return AUDIT_HEAD + 2 * R
 
 
-class raft_monitor_config(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("leaderless_steps", "stalled_steps", "lag_entries", "churn_terms",
-                                         "churn_steps")] + [("reserved", C.c_int32 * 3)]
-
-
-class raft_monitor_info(C.Structure):
-    _fields_ = [(k, C.c_int64) for k in ("flagged", "newly_flagged", "cleared", "leaderless", "commit_stalled", "lagging",
-                                         "churning", "down", "outages_ended", "down_steps_ended")] + [
-        ("reserved", C.c_int64 * 2)]
-
-
-class raft_monitor_event(C.Structure):
-    _fields_ = [("group", C.c_int64)] + [(k, C.c_int32) for k in ("now", "ever", "down_since", "stall_since", "leader",
-                                                                  "lag_mask")]
-
-
-class raft_monitor_report_info(C.Structure):
-    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("flagged", C.c_int64), ("reserved", C.c_int64 * 5)]
-
-
-class raft_monitor_availability(C.Structure):
-    _fields_ = [("hist", C.c_int64 * 32), ("outages", C.c_int64), ("down_steps", C.c_int64), ("reserved", C.c_int64 * 2)]
-
-
-# the liveness monitor (raft_monitor_*): the bits of a ledger's now / ever words in the order of raft_monitor_info's
-# per-kind counts, the report's word selector, raft_monitor_event as a numpy record (32 bytes, no padding), the
-# thresholds of a config, the names of a group's 16 exported ledger words
+# the liveness monitor (raft_monitor_*): the thresholds of a config, the bits of a ledger's now / ever words in
+# the order of raft_monitor_info's per-kind counts, the report's word selector, raft_monitor_event (32 bytes), the
+# names of a group's 16 exported ledger words
+raft_monitor_config = record("raft_monitor_config", ("leaderless_steps stalled_steps lag_entries churn_terms "
+                                                     "churn_steps reserved[3]", I32))
+raft_monitor_info = record("raft_monitor_info", ("flagged newly_flagged cleared leaderless commit_stalled lagging "
+                                                 "churning down outages_ended down_steps_ended reserved[2]", I64))
+raft_monitor_event = record("raft_monitor_event", ("group", I64), ("now ever down_since stall_since leader lag_mask", I32))
+raft_monitor_report_info = record("raft_monitor_report_info", ("delivered pending flagged reserved[5]", I64))
+raft_monitor_availability = record("raft_monitor_availability", ("hist[32] outages down_steps reserved[2]", I64))
 MONITOR_LEADERLESS, MONITOR_COMMIT_STALLED, MONITOR_LAGGING, MONITOR_CHURNING = 1, 2, 4, 8
-MONITOR_KINDS = ("leaderless", "commit_stalled", "lagging", "churning")
+MONITOR_KINDS = raft_monitor_info.scalars[3:7]
 MONITOR_ALL = 15
 MONITOR_NOW, MONITOR_EVER = 0, 1
-MONITOR_INFO_FIELDS = ("flagged", "newly_flagged", "cleared") + MONITOR_KINDS + ("down", "outages_ended",
-                                                                               "down_steps_ended")
-MONITOR_REPORT_FIELDS = ("delivered", "pending", "flagged")
-MONITOR_EVENT_DTYPE = np.dtype([("group", np.int64), ("now", np.int32), ("ever", np.int32), ("down_since", np.int32),
-                                ("stall_since", np.int32), ("leader", np.int32), ("lag_mask", np.int32)])
-MONITOR_CONFIG_FIELDS = ("leaderless_steps", "stalled_steps", "lag_entries", "churn_terms", "churn_steps")
+MONITOR_INFO_FIELDS = raft_monitor_info.scalars
+MONITOR_REPORT_FIELDS = raft_monitor_report_info.scalars
+MONITOR_EVENT_DTYPE = raft_monitor_event.dtype
+MONITOR_CONFIG_FIELDS = raft_monitor_config.scalars
 MONITOR_STALLED_STEPS = 16   # RaftEngine.monitor's default stalled_steps
 MONITOR_WORD_NAMES = ("now", "ever", "first_step", "leader", "down_since", "outages", "down_total", "longest",
                       "stall_since", "stall_mark", "win_start", "win_term", "lag_mask", "max_lag", "reserved0",
@@ -429,61 +324,35 @@ MONITOR_WORD_NAMES = ("now", "ever", "first_step", "leader", "down_since", "outa
 MONITOR_WORDS = 16
 MONITOR_HIST = 32
 
-
-class raft_wal_cursor(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("term", "vote", "stable", "stable_term", "floor", "pad")]
-
-
-class raft_wal_record(C.Structure):
-    _fields_ = [("group", C.c_int32), ("replica", C.c_int16), ("kind", C.c_int16), ("index", C.c_int32),
-                ("term", C.c_int32), ("cmd", C.c_uint32), ("aux", C.c_int32)]
-
-
-class raft_wal_info(C.Structure):
-    _fields_ = [(k, C.c_int64) for k in ("delivered", "pending", "hardstates", "truncates", "entries", "lost",
-                                         "regressed")]
-
-
-# the persistence stream (raft_wal_*): the record kinds, raft_wal_record and raft_wal_cursor as numpy records (24
-# bytes each, no padding), the fields of raft_wal_info, a fresh cursor
+# the persistence stream (raft_wal_*): raft_wal_record and raft_wal_cursor (24 bytes each), the info, the record
+# kinds, a fresh cursor
+raft_wal_cursor = record("raft_wal_cursor", ("term vote stable stable_term floor pad", I32))
+raft_wal_record = record("raft_wal_record", ("group", I32), ("replica kind", I16), ("index term", I32), ("cmd", U32),
+                         ("aux", I32))
+raft_wal_info = record("raft_wal_info", ("delivered pending hardstates truncates entries lost regressed", I64))
 WAL_HARDSTATE, WAL_TRUNCATE, WAL_ENTRY = 0, 1, 2
 WAL_KIND_NAMES = ["HARDSTATE", "TRUNCATE", "ENTRY"]
-WAL_RECORD_DTYPE = np.dtype([("group", np.int32), ("replica", np.int16), ("kind", np.int16), ("index", np.int32),
-                             ("term", np.int32), ("cmd", np.uint32), ("aux", np.int32)])
-WAL_CURSOR_DTYPE = np.dtype([("term", np.int32), ("vote", np.int32), ("stable", np.int32), ("stable_term", np.int32),
-                             ("floor", np.int32), ("pad", np.int32)])
-WAL_INFO_FIELDS = ("delivered", "pending", "hardstates", "truncates", "entries", "lost", "regressed")
+WAL_RECORD_DTYPE = raft_wal_record.dtype
+WAL_CURSOR_DTYPE = raft_wal_cursor.dtype
+WAL_INFO_FIELDS = raft_wal_info.scalars
 WAL_FRESH = (0, -1, 0, 0, 0, 0)
 
-
-class raft_isolate_ticket(C.Structure):
-    _fields_ = [("replica", C.c_int32), ("steps", C.c_int32), ("status", C.c_int32), ("prev", C.c_int32)]
-
-
-class raft_heal_info(C.Structure):
-    _fields_ = [("healed", C.c_int64), ("idle", C.c_int64), ("kept", C.c_int64), ("reserved", C.c_int64)]
-
-
-class raft_isolated(C.Structure):
-    _fields_ = [("group", C.c_int64), ("replica", C.c_int16), ("role", C.c_int16), ("remaining", C.c_int32)]
-
-
-class raft_isolated_info(C.Structure):
-    _fields_ = [("delivered", C.c_int64), ("pending", C.c_int64), ("running", C.c_int64), ("reserved", C.c_int64)]
-
-
-# scripted network faults (raft_isolate_batch*, raft_engine_heal_network*, raft_engine_list_isolated*): the leader
-# selectors of a target, the flag, the largest steps, raft_isolate_ticket.status, the ticket and raft_isolated as
-# numpy records (16 bytes each, no padding), the fields of the two infos
+# scripted network faults (raft_isolate_batch*, raft_engine_heal_network*, raft_engine_list_isolated*): the ticket
+# and raft_isolated (16 bytes each), the two infos, the leader selectors of a target, the flag, the largest steps,
+# raft_isolate_ticket.status
+raft_isolate_ticket = record("raft_isolate_ticket", ("replica steps status prev", I32))
+raft_heal_info = record("raft_heal_info", ("healed idle kept reserved", I64))
+raft_isolated = record("raft_isolated", ("group", I64), ("replica role", I16), ("remaining", I32))
+raft_isolated_info = record("raft_isolated_info", ("delivered pending running reserved", I64))
 ISOLATE_NEWEST_LEADER, ISOLATE_LOWEST_LEADER = -1, -2
 ISOLATE_REPLACE = 1
 ISOLATE_MAX_STEPS = (1 << 23) - 1
 ISOLATE_SET, ISOLATE_BUSY, ISOLATE_NO_LEADER, ISOLATE_DUPLICATE, ISOLATE_INVALID = range(5)
 ISOLATE_STATUS_NAMES = ["SET", "BUSY", "NO_LEADER", "DUPLICATE", "INVALID"]
-ISOLATE_TICKET_DTYPE = np.dtype([("replica", np.int32), ("steps", np.int32), ("status", np.int32), ("prev", np.int32)])
-ISOLATED_DTYPE = np.dtype([("group", np.int64), ("replica", np.int16), ("role", np.int16), ("remaining", np.int32)])
-HEAL_INFO_FIELDS = ("healed", "idle", "kept")
-ISOLATED_INFO_FIELDS = ("delivered", "pending", "running")
+ISOLATE_TICKET_DTYPE = raft_isolate_ticket.dtype
+ISOLATED_DTYPE = raft_isolated.dtype
+HEAL_INFO_FIELDS = raft_heal_info.scalars
+ISOLATED_INFO_FIELDS = raft_isolated_info.scalars
 
 
 # the reference's hard-coded constants
@@ -540,6 +409,162 @@ def ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def _signatures() -> dict:
+    """name -> (restype, argtypes) of every function include/*.h declares
+    (tests/test_abi.py holds the keys to the headers)."""
+    P, INT, VP, U8 = C.POINTER, C.c_int, C.c_void_p, C.c_uint8
+    eng = VP
+    batch3 = (INT, [eng, VP, VP, VP, I64])                   # (engine, three device or host vectors, n)
+    batch4 = (INT, [eng, VP, VP, VP, VP, I64])
+    ranged = (INT, [VP, I64, I64, P(I32)])                   # (handle, g0, n, int32 words)
+
+    def stream(handle, info, *sel):
+        """(handle, g0, n, selectors..., records, room, info): an ordered record stream."""
+        return (INT, [handle, I64, I64, *sel, VP, I64, P(info)])
+
+    return {
+        "raft_params_default": (None, [P(raft_params)]),
+        "raft_last_error": (C.c_char_p, []),
+        "raft_abi_version": (INT, []),
+        "raft_build_source_id": (C.c_char_p, []),
+        "raft_build_kernel_source_id": (C.c_char_p, []),
+        "raft_build_batch_source_id": (C.c_char_p, []),
+        "raft_engine_create": (INT, [P(raft_params), INT, P(eng)]),
+        "raft_engine_destroy": (INT, [eng]),
+        "raft_engine_step": (INT, [eng, I32, P(I64)]),
+        "raft_engine_step_async": (INT, [eng, I32, VP]),
+        "raft_engine_sync": (INT, [eng]),
+        "raft_engine_stream": (VP, [eng]),
+        "raft_engine_set_kernel_timing": (INT, [eng, INT]),
+        "raft_engine_kernel_time": (INT, [eng, P(C.c_double), P(I64)]),
+        "raft_engine_timed_span": (INT, [eng, VP, P(C.c_double)]),
+        "raft_engine_step_index": (I64, [eng]),
+        "raft_engine_set_step_index": (INT, [eng, I64]),
+        "raft_engine_set_steps_per_launch": (INT, [eng, I32]),
+        "raft_engine_set_subranges": (INT, [eng, I32]),
+        "raft_engine_subranges": (I32, [eng]),
+        "raft_engine_kernel_info": (INT, [eng, P(raft_kernel_info)]),
+        "raft_engine_wait_stream": (INT, [eng, VP]),
+        "raft_engine_set_kernel": (INT, [eng, I32]),
+        "raft_engine_set_batch_path": (INT, [eng, I32]),
+        "raft_engine_reset": (INT, [eng]),
+        "raft_engine_trim_staging": (INT, [eng]),
+        "raft_engine_device_bytes": (I64, [eng]),
+        "raft_engine_read_state": ranged,
+        "raft_engine_write_state": ranged,
+        "raft_engine_read_log": (INT, [eng, I64, I64, P(I32), P(U32)]),
+        "raft_engine_write_log": (INT, [eng, I64, I64, P(I32), P(U32)]),
+        "raft_engine_digest": (INT, [eng, P(U64)]),
+        "raft_engine_digest_range": (INT, [eng, I64, I64, P(U64)]),
+        "raft_engine_check_log_matching": (INT, [eng, I64, I64, P(U8), P(I64)]),
+        "raft_engine_traffic_probe": (INT, [eng, I32, P(I64), P(I64)]),
+        "raft_engine_drain_committed": stream(eng, raft_drain_info, I32),
+        "raft_engine_drain_committed_dev": stream(eng, raft_drain_info, I32),
+        "raft_engine_read_applied": ranged,
+        "raft_engine_write_applied": ranged,
+        "raft_engine_read_leaders": (INT, [eng, I64, I64, VP]),
+        "raft_propose_batch": batch3,
+        "raft_propose_batch_dev": batch3,
+        "raft_engine_resolve_tickets": batch4,
+        "raft_engine_resolve_tickets_dev": batch4,
+        "raft_engine_sm_configure": (INT, [eng, I32]),
+        "raft_engine_sm_apply": (INT, [eng, I64, I64, I32, P(raft_sm_info)]),
+        "raft_engine_sm_read": (INT, [eng, I64, I64, VP, VP]),
+        "raft_engine_sm_write": (INT, [eng, I64, I64, VP, VP]),
+        "raft_engine_sm_get": batch4,
+        "raft_engine_sm_check": (INT, [eng, I64, I64, P(U8), P(I64)]),
+        "raft_engine_restart": (INT, [eng, I64, I64, VP, I32, I32, P(raft_restart_info)]),
+        "raft_engine_restart_dev": (INT, [eng, I64, I64, VP, I32, I32, P(raft_restart_info)]),
+        "raft_engine_restart_random": (INT, [eng, I64, I64, U32, I32, I32, P(raft_restart_info)]),
+        "raft_engine_install_snapshot": (INT, [eng, I64, I64, VP, I32, P(raft_install_info)]),
+        "raft_engine_install_snapshot_dev": (INT, [eng, I64, I64, VP, I32, P(raft_install_info)]),
+        "raft_read_begin_batch": (INT, [eng, VP, VP, I64]),
+        "raft_read_begin_batch_dev": (INT, [eng, VP, VP, I64]),
+        "raft_read_serve_batch": batch4,
+        "raft_read_serve_batch_dev": batch4,
+        "raft_transfer_batch": batch3,
+        "raft_transfer_batch_dev": batch3,
+        "raft_engine_resolve_transfers": batch3,
+        "raft_engine_resolve_transfers_dev": batch3,
+        "raft_engine_evacuate": (INT, [eng, I64, I64, VP, P(raft_evacuate_info)]),
+        "raft_engine_evacuate_dev": (INT, [eng, I64, I64, VP, P(raft_evacuate_info)]),
+        "raft_engine_append_noops": (INT, [eng, I64, I64, U32, VP, VP, P(raft_noop_info)]),
+        "raft_engine_append_noops_dev": (INT, [eng, I64, I64, U32, VP, VP, P(raft_noop_info)]),
+        "raft_engine_sm_set_noop": (INT, [eng, INT, U32]),
+        "raft_engine_poll_leaders": stream(eng, raft_watch_info),
+        "raft_engine_poll_leaders_dev": stream(eng, raft_watch_info),
+        "raft_engine_read_watch": ranged,
+        "raft_engine_write_watch": ranged,
+        "raft_engine_outbox_configure": (INT, [eng, I64, I32]),
+        "raft_outbox_submit": batch3,
+        "raft_outbox_submit_dev": batch3,
+        "raft_engine_outbox_pump": (INT, [eng, VP, I64, P(I64), P(raft_outbox_info)]),
+        "raft_engine_outbox_pump_dev": (INT, [eng, VP, I64, P(I64), P(raft_outbox_info)]),
+        "raft_engine_outbox_read": (INT, [eng, VP, I64, P(I64)]),
+        "raft_engine_outbox_write": (INT, [eng, VP, I64]),
+        "raft_audit_create": (INT, [eng, P(VP)]),
+        "raft_audit_destroy": (INT, [VP]),
+        "raft_audit_reset": (INT, [VP]),
+        "raft_audit_device_bytes": (I64, [VP]),
+        "raft_audit_observe": (INT, [VP, I64, I64, P(raft_audit_info)]),
+        "raft_audit_report": stream(VP, raft_audit_report_info),
+        "raft_audit_report_dev": stream(VP, raft_audit_report_info),
+        "raft_audit_read": ranged,
+        "raft_audit_write": ranged,
+        "raft_monitor_create": (INT, [eng, P(raft_monitor_config), P(VP)]),
+        "raft_monitor_destroy": (INT, [VP]),
+        "raft_monitor_reset": (INT, [VP]),
+        "raft_monitor_device_bytes": (I64, [VP]),
+        "raft_monitor_observe": (INT, [VP, I64, I64, P(raft_monitor_info)]),
+        "raft_monitor_report": stream(VP, raft_monitor_report_info, I32, I32),
+        "raft_monitor_report_dev": stream(VP, raft_monitor_report_info, I32, I32),
+        "raft_monitor_get_availability": (INT, [VP, P(raft_monitor_availability)]),
+        "raft_monitor_set_availability": (INT, [VP, P(raft_monitor_availability)]),
+        "raft_monitor_read": ranged,
+        "raft_monitor_write": ranged,
+        "raft_wal_create": (INT, [eng, P(VP)]),
+        "raft_wal_destroy": (INT, [VP]),
+        "raft_wal_reset": (INT, [VP]),
+        "raft_wal_device_bytes": (I64, [VP]),
+        "raft_wal_poll": stream(VP, raft_wal_info, I32),
+        "raft_wal_poll_dev": stream(VP, raft_wal_info, I32),
+        "raft_wal_read": (INT, [VP, I64, I64, VP]),
+        "raft_wal_write": (INT, [VP, I64, I64, VP]),
+        "raft_isolate_batch": (INT, [eng, VP, VP, VP, I32, VP, I64]),
+        "raft_isolate_batch_dev": (INT, [eng, VP, VP, VP, I32, VP, I64]),
+        "raft_engine_heal_network": (INT, [eng, I64, I64, VP, P(raft_heal_info)]),
+        "raft_engine_heal_network_dev": (INT, [eng, I64, I64, VP, P(raft_heal_info)]),
+        "raft_engine_list_isolated": stream(eng, raft_isolated_info),
+        "raft_engine_list_isolated_dev": stream(eng, raft_isolated_info),
+        "raft_comm_get_unique_id": (INT, [P(U8)]),
+        "raft_comm_create": (INT, [P(U8), I32, I32, INT, P(VP)]),
+        "raft_comm_destroy": (INT, [VP]),
+        "raft_engine_allreduce_counters": (INT, [eng, VP, VP, VP, I32]),
+        "raft_vote_batch": (INT, [eng, P(I64), P(I32), P(raft_vote_req), P(raft_vote_resp), I64]),
+        "raft_append_batch": (INT, [eng, P(I64), P(I32), P(raft_append_req), P(raft_append_resp), I64]),
+        "raft_append_command_batch": (INT, [eng, P(I64), P(I32), P(U32), I64]),
+        "raft_vote_batch_dev": batch4,
+        "raft_append_batch_dev": batch4,
+        "raft_append_command_batch_dev": batch3,
+        "raft_philox4x32_10": (None, [P(U32), P(U32), P(U32)]),
+        "raft_host_alloc": (VP, [I64]),
+        "raft_host_free": (INT, [VP]),
+        # include/raft_wire.h
+        "raft_wire_decode_vote_req": (INT, [P(U8), P(I64), I64, P(raft_vote_req)]),
+        "raft_wire_encode_vote_req": (I64, [P(raft_vote_req), I64, P(U8), I64, P(I64)]),
+        "raft_wire_decode_vote_resp": (INT, [P(U8), P(I64), I64, P(raft_vote_resp)]),
+        "raft_wire_encode_vote_resp": (I64, [P(raft_vote_resp), I64, P(U8), I64, P(I64)]),
+        "raft_wire_decode_append_req": (INT, [P(U8), P(I64), I64, P(raft_append_req), P(I64), P(I32), P(I32)]),
+        "raft_wire_encode_append_req": (I64, [P(raft_append_req), P(U8), P(I64), I64, P(U8), I64, P(I64)]),
+        "raft_wire_decode_append_resp": (INT, [P(U8), P(I64), I64, P(raft_append_resp)]),
+        "raft_wire_encode_append_resp": (I64, [P(raft_append_resp), I64, P(U8), I64, P(I64)]),
+    }
+
+
+SIGNATURES = _signatures()
+# symbols declared in include/*.h (checked by tests/test_abi.py)
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -586,150 +611,7 @@ def load_library(path: str | None = None):
     lib = C.CDLL(p)
     if path is None and not os.environ.get("RAFT_ENGINE_LIB"):
         check_build(lib, p)
-    P, I32, I64, U64 = C.POINTER, C.c_int32, C.c_int64, C.c_uint64
-    eng = C.c_void_p
-    sig = {
-        "raft_params_default": (None, [P(raft_params)]),
-        "raft_last_error": (C.c_char_p, []),
-        "raft_abi_version": (C.c_int, []),
-        "raft_build_source_id": (C.c_char_p, []),
-        "raft_build_kernel_source_id": (C.c_char_p, []),
-        "raft_build_batch_source_id": (C.c_char_p, []),
-        "raft_engine_create": (C.c_int, [P(raft_params), C.c_int, P(eng)]),
-        "raft_engine_destroy": (C.c_int, [eng]),
-        "raft_engine_step": (C.c_int, [eng, I32, P(I64)]),
-        "raft_engine_step_async": (C.c_int, [eng, I32, C.c_void_p]),
-        "raft_engine_sync": (C.c_int, [eng]),
-        "raft_engine_stream": (C.c_void_p, [eng]),
-        "raft_engine_set_kernel_timing": (C.c_int, [eng, C.c_int]),
-        "raft_engine_kernel_time": (C.c_int, [eng, P(C.c_double), P(I64)]),
-        "raft_engine_timed_span": (C.c_int, [eng, C.c_void_p, P(C.c_double)]),
-        "raft_engine_step_index": (I64, [eng]),
-        "raft_engine_set_step_index": (C.c_int, [eng, I64]),
-        "raft_engine_set_steps_per_launch": (C.c_int, [eng, I32]),
-        "raft_engine_set_subranges": (C.c_int, [eng, I32]),
-        "raft_engine_subranges": (I32, [eng]),
-        "raft_engine_kernel_info": (C.c_int, [eng, P(raft_kernel_info)]),
-        "raft_engine_wait_stream": (C.c_int, [eng, C.c_void_p]),
-        "raft_engine_set_kernel": (C.c_int, [eng, I32]),
-        "raft_engine_set_batch_path": (C.c_int, [eng, I32]),
-        "raft_engine_reset": (C.c_int, [eng]),
-        "raft_engine_trim_staging": (C.c_int, [eng]),
-        "raft_engine_device_bytes": (I64, [eng]),
-        "raft_engine_read_state": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_write_state": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_read_log": (C.c_int, [eng, I64, I64, P(I32), P(C.c_uint32)]),
-        "raft_engine_write_log": (C.c_int, [eng, I64, I64, P(I32), P(C.c_uint32)]),
-        "raft_engine_digest": (C.c_int, [eng, P(U64)]),
-        "raft_engine_digest_range": (C.c_int, [eng, I64, I64, P(U64)]),
-        "raft_engine_check_log_matching": (C.c_int, [eng, I64, I64, P(C.c_uint8), P(I64)]),
-        "raft_engine_traffic_probe": (C.c_int, [eng, I32, P(I64), P(I64)]),
-        "raft_engine_drain_committed": (C.c_int, [eng, I64, I64, I32, C.c_void_p, I64, P(raft_drain_info)]),
-        "raft_engine_drain_committed_dev": (C.c_int, [eng, I64, I64, I32, C.c_void_p, I64, P(raft_drain_info)]),
-        "raft_engine_read_applied": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_write_applied": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_read_leaders": (C.c_int, [eng, I64, I64, C.c_void_p]),
-        "raft_propose_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_propose_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_resolve_tickets": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_resolve_tickets_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_sm_configure": (C.c_int, [eng, I32]),
-        "raft_engine_sm_apply": (C.c_int, [eng, I64, I64, I32, P(raft_sm_info)]),
-        "raft_engine_sm_read": (C.c_int, [eng, I64, I64, C.c_void_p, C.c_void_p]),
-        "raft_engine_sm_write": (C.c_int, [eng, I64, I64, C.c_void_p, C.c_void_p]),
-        "raft_engine_sm_get": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_sm_check": (C.c_int, [eng, I64, I64, P(C.c_uint8), P(I64)]),
-        "raft_engine_restart": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
-        "raft_engine_restart_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, I32, P(raft_restart_info)]),
-        "raft_engine_restart_random": (C.c_int, [eng, I64, I64, C.c_uint32, I32, I32, P(raft_restart_info)]),
-        "raft_engine_install_snapshot": (C.c_int, [eng, I64, I64, C.c_void_p, I32, P(raft_install_info)]),
-        "raft_engine_install_snapshot_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I32, P(raft_install_info)]),
-        "raft_read_begin_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
-        "raft_read_begin_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, I64]),
-        "raft_read_serve_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_read_serve_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_transfer_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_transfer_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_resolve_transfers": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_resolve_transfers_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_evacuate": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
-        "raft_engine_evacuate_dev": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_evacuate_info)]),
-        "raft_engine_append_noops": (C.c_int, [eng, I64, I64, C.c_uint32, C.c_void_p, C.c_void_p, P(raft_noop_info)]),
-        "raft_engine_append_noops_dev": (C.c_int, [eng, I64, I64, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                   P(raft_noop_info)]),
-        "raft_engine_sm_set_noop": (C.c_int, [eng, C.c_int, C.c_uint32]),
-        "raft_engine_poll_leaders": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_watch_info)]),
-        "raft_engine_poll_leaders_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_watch_info)]),
-        "raft_engine_read_watch": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_write_watch": (C.c_int, [eng, I64, I64, P(I32)]),
-        "raft_engine_outbox_configure": (C.c_int, [eng, I64, I32]),
-        "raft_outbox_submit": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_outbox_submit_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_engine_outbox_pump": (C.c_int, [eng, C.c_void_p, I64, P(I64), P(raft_outbox_info)]),
-        "raft_engine_outbox_pump_dev": (C.c_int, [eng, C.c_void_p, I64, P(I64), P(raft_outbox_info)]),
-        "raft_engine_outbox_read": (C.c_int, [eng, C.c_void_p, I64, P(I64)]),
-        "raft_engine_outbox_write": (C.c_int, [eng, C.c_void_p, I64]),
-        "raft_audit_create": (C.c_int, [eng, P(C.c_void_p)]),
-        "raft_audit_destroy": (C.c_int, [C.c_void_p]),
-        "raft_audit_reset": (C.c_int, [C.c_void_p]),
-        "raft_audit_device_bytes": (I64, [C.c_void_p]),
-        "raft_audit_observe": (C.c_int, [C.c_void_p, I64, I64, P(raft_audit_info)]),
-        "raft_audit_report": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p, I64, P(raft_audit_report_info)]),
-        "raft_audit_report_dev": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p, I64, P(raft_audit_report_info)]),
-        "raft_audit_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
-        "raft_audit_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
-        "raft_monitor_create": (C.c_int, [eng, P(raft_monitor_config), P(C.c_void_p)]),
-        "raft_monitor_destroy": (C.c_int, [C.c_void_p]),
-        "raft_monitor_reset": (C.c_int, [C.c_void_p]),
-        "raft_monitor_device_bytes": (I64, [C.c_void_p]),
-        "raft_monitor_observe": (C.c_int, [C.c_void_p, I64, I64, P(raft_monitor_info)]),
-        "raft_monitor_report": (C.c_int, [C.c_void_p, I64, I64, I32, I32, C.c_void_p, I64, P(raft_monitor_report_info)]),
-        "raft_monitor_report_dev": (C.c_int, [C.c_void_p, I64, I64, I32, I32, C.c_void_p, I64,
-                                              P(raft_monitor_report_info)]),
-        "raft_monitor_get_availability": (C.c_int, [C.c_void_p, P(raft_monitor_availability)]),
-        "raft_monitor_set_availability": (C.c_int, [C.c_void_p, P(raft_monitor_availability)]),
-        "raft_monitor_read": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
-        "raft_monitor_write": (C.c_int, [C.c_void_p, I64, I64, P(I32)]),
-        "raft_wal_create": (C.c_int, [eng, P(C.c_void_p)]),
-        "raft_wal_destroy": (C.c_int, [C.c_void_p]),
-        "raft_wal_reset": (C.c_int, [C.c_void_p]),
-        "raft_wal_device_bytes": (I64, [C.c_void_p]),
-        "raft_wal_poll": (C.c_int, [C.c_void_p, I64, I64, I32, C.c_void_p, I64, P(raft_wal_info)]),
-        "raft_wal_poll_dev": (C.c_int, [C.c_void_p, I64, I64, I32, C.c_void_p, I64, P(raft_wal_info)]),
-        "raft_wal_read": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
-        "raft_wal_write": (C.c_int, [C.c_void_p, I64, I64, C.c_void_p]),
-        "raft_isolate_batch": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I32, C.c_void_p, I64]),
-        "raft_isolate_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I32, C.c_void_p, I64]),
-        "raft_engine_heal_network": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_heal_info)]),
-        "raft_engine_heal_network_dev": (C.c_int, [eng, I64, I64, C.c_void_p, P(raft_heal_info)]),
-        "raft_engine_list_isolated": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_isolated_info)]),
-        "raft_engine_list_isolated_dev": (C.c_int, [eng, I64, I64, C.c_void_p, I64, P(raft_isolated_info)]),
-        "raft_comm_get_unique_id": (C.c_int, [P(C.c_uint8)]),
-        "raft_comm_create": (C.c_int, [P(C.c_uint8), I32, I32, C.c_int, P(C.c_void_p)]),
-        "raft_comm_destroy": (C.c_int, [C.c_void_p]),
-        "raft_engine_allreduce_counters": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I32]),
-        "raft_vote_batch": (C.c_int, [eng, P(I64), P(I32), P(raft_vote_req), P(raft_vote_resp), I64]),
-        "raft_append_batch": (C.c_int, [eng, P(I64), P(I32), P(raft_append_req), P(raft_append_resp), I64]),
-        "raft_append_command_batch": (C.c_int, [eng, P(I64), P(I32), P(C.c_uint32), I64]),
-        "raft_vote_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_append_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_append_command_batch_dev": (C.c_int, [eng, C.c_void_p, C.c_void_p, C.c_void_p, I64]),
-        "raft_philox4x32_10": (None, [P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
-        "raft_host_alloc": (C.c_void_p, [I64]),
-        "raft_host_free": (C.c_int, [C.c_void_p]),
-        # include/raft_wire.h
-        "raft_wire_decode_vote_req": (C.c_int, [P(C.c_uint8), P(I64), I64, P(raft_vote_req)]),
-        "raft_wire_encode_vote_req": (I64, [P(raft_vote_req), I64, P(C.c_uint8), I64, P(I64)]),
-        "raft_wire_decode_vote_resp": (C.c_int, [P(C.c_uint8), P(I64), I64, P(raft_vote_resp)]),
-        "raft_wire_encode_vote_resp": (I64, [P(raft_vote_resp), I64, P(C.c_uint8), I64, P(I64)]),
-        "raft_wire_decode_append_req": (C.c_int, [P(C.c_uint8), P(I64), I64, P(raft_append_req), P(I64), P(I32),
-                                                  P(I32)]),
-        "raft_wire_encode_append_req": (I64, [P(raft_append_req), P(C.c_uint8), P(I64), I64, P(C.c_uint8), I64,
-                                              P(I64)]),
-        "raft_wire_decode_append_resp": (C.c_int, [P(C.c_uint8), P(I64), I64, P(raft_append_resp)]),
-        "raft_wire_encode_append_resp": (I64, [P(raft_append_resp), I64, P(C.c_uint8), I64, P(I64)]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         if os.environ.get("RAFT_ENGINE_LIB") and not hasattr(lib, name):
             # an older experimental build (RAFT_ENGINE_LIB) may lack newer
             # entry points: bind a stub that says so when it is called
@@ -741,48 +623,3 @@ def load_library(path: str | None = None):
         f.argtypes = args
     _lib = lib if path is None else _lib
     return lib
-
-
-# symbols declared in include/*.h (checked by tests/test_abi.py)
-EXPORTED_SYMBOLS = [
-    "raft_params_default", "raft_last_error", "raft_abi_version", "raft_build_source_id",
-    "raft_build_kernel_source_id", "raft_build_batch_source_id", "raft_engine_create",
-    "raft_engine_destroy", "raft_engine_step", "raft_engine_step_async", "raft_engine_sync",
-    "raft_engine_stream", "raft_engine_set_kernel_timing", "raft_engine_kernel_time", "raft_engine_timed_span",
-    "raft_engine_step_index", "raft_engine_set_step_index", "raft_engine_set_steps_per_launch",
-    "raft_engine_set_subranges", "raft_engine_subranges", "raft_engine_kernel_info", "raft_engine_wait_stream",
-    "raft_engine_set_kernel", "raft_engine_set_batch_path", "raft_engine_reset", "raft_engine_trim_staging",
-    "raft_engine_device_bytes",
-    "raft_engine_read_state", "raft_engine_write_state", "raft_engine_read_log",
-    "raft_engine_write_log", "raft_engine_digest", "raft_engine_digest_range", "raft_engine_check_log_matching", "raft_engine_traffic_probe",
-    "raft_engine_drain_committed", "raft_engine_drain_committed_dev", "raft_engine_read_applied", "raft_engine_write_applied",
-    "raft_engine_read_leaders", "raft_propose_batch", "raft_propose_batch_dev", "raft_engine_resolve_tickets",
-    "raft_engine_resolve_tickets_dev",
-    "raft_engine_sm_configure", "raft_engine_sm_apply", "raft_engine_sm_read", "raft_engine_sm_write",
-    "raft_engine_sm_get", "raft_engine_sm_check",
-    "raft_engine_restart", "raft_engine_restart_dev", "raft_engine_restart_random",
-    "raft_engine_install_snapshot", "raft_engine_install_snapshot_dev",
-    "raft_read_begin_batch", "raft_read_begin_batch_dev", "raft_read_serve_batch", "raft_read_serve_batch_dev",
-    "raft_transfer_batch", "raft_transfer_batch_dev", "raft_engine_resolve_transfers",
-    "raft_engine_resolve_transfers_dev", "raft_engine_evacuate", "raft_engine_evacuate_dev",
-    "raft_engine_append_noops", "raft_engine_append_noops_dev", "raft_engine_sm_set_noop",
-    "raft_engine_poll_leaders", "raft_engine_poll_leaders_dev", "raft_engine_read_watch", "raft_engine_write_watch",
-    "raft_engine_outbox_configure", "raft_outbox_submit", "raft_outbox_submit_dev", "raft_engine_outbox_pump",
-    "raft_engine_outbox_pump_dev", "raft_engine_outbox_read", "raft_engine_outbox_write",
-    "raft_audit_create", "raft_audit_destroy", "raft_audit_reset", "raft_audit_device_bytes", "raft_audit_observe",
-    "raft_audit_report", "raft_audit_report_dev", "raft_audit_read", "raft_audit_write",
-    "raft_monitor_create", "raft_monitor_destroy", "raft_monitor_reset", "raft_monitor_device_bytes",
-    "raft_monitor_observe", "raft_monitor_report", "raft_monitor_report_dev", "raft_monitor_get_availability",
-    "raft_monitor_set_availability", "raft_monitor_read", "raft_monitor_write",
-    "raft_wal_create", "raft_wal_destroy", "raft_wal_reset", "raft_wal_device_bytes", "raft_wal_poll",
-    "raft_wal_poll_dev", "raft_wal_read", "raft_wal_write",
-    "raft_isolate_batch", "raft_isolate_batch_dev", "raft_engine_heal_network", "raft_engine_heal_network_dev",
-    "raft_engine_list_isolated", "raft_engine_list_isolated_dev",
-    "raft_comm_get_unique_id", "raft_comm_create", "raft_comm_destroy", "raft_engine_allreduce_counters", "raft_vote_batch", "raft_append_batch",
-    "raft_append_command_batch", "raft_vote_batch_dev", "raft_append_batch_dev", "raft_append_command_batch_dev",
-    "raft_philox4x32_10", "raft_host_alloc", "raft_host_free",
-    # include/raft_wire.h
-    "raft_wire_decode_vote_req", "raft_wire_encode_vote_req", "raft_wire_decode_vote_resp",
-    "raft_wire_encode_vote_resp", "raft_wire_decode_append_req", "raft_wire_encode_append_req",
-    "raft_wire_decode_append_resp", "raft_wire_encode_append_resp",
-]

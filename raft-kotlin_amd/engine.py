@@ -24,6 +24,106 @@ class RaftError(RuntimeError):
     pass
 
 
+# -- what the wrappers share: argument checks, the DEVICE-pointer prologue, the record streams ---------------
+def _int(what: str, name: str, v, lo=None, hi=None, allow_none: bool = False, want: str | None = None):
+    """v as an int (None stays None with allow_none), or a ValueError that
+    starts with the method's name.  A bool is never an integer; lo / hi bound
+    the value (both inclusive); `want` words the message's demand."""
+    if v is None and allow_none:
+        return None
+    if (isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+            and (lo is None or v >= lo) and (hi is None or v <= hi)):
+        return int(v)
+    if want is None:
+        want = "an integer" + (f" in {lo}..{hi}" if hi is not None else f" >= {lo}" if lo is not None else "")
+    raise ValueError(f"{what}: {name} must be {'None or ' if allow_none else ''}{want}, not {v!r}")
+
+
+def _span(what: str, G: int, g0, n):
+    """The group range [g0, g0 + n) of a call (n None: up to group G) as two
+    ints.  Whether it lies inside the engine is the library's to refuse."""
+    g0 = _int(what, "g0", g0)
+    return g0, _int(what, "n", G - g0 if n is None else n)
+
+
+def _dev_prologue(what: str, ptrs: dict, align: int = 16, after_stream=None, wait=None):
+    """What a call on DEVICE pointers does first: the alignment of the named
+    buffers, then `wait(after_stream)` (RaftEngine.wait_stream) when a stream
+    was given."""
+    if any(p % align for p in ptrs.values()):
+        raise ValueError(f"{what}: the {' and '.join(ptrs)} buffer{'s' if len(ptrs) > 1 else ''} must be "
+                         f"{align}-byte aligned")
+    if after_stream is not None:
+        wait(after_stream)
+
+
+def _stream_call(owner, name: str, *args):
+    """The closure a _RecordStream drives: one call of owner's entry point
+    `name` (handle, *args, records, room, info), which returns its code.  The
+    library is looked up when it is called, after every argument check."""
+    return lambda out, room, info: getattr(owner._lib, name)(owner._h, *args, out, room, info)
+
+
+class _RecordStream:
+    """The protocol of every entry point that hands out ordered records cut at
+    a room limit (include/raft_engine.h: drain_committed, poll_leaders,
+    list_isolated, audit / monitor report, wal_poll), in one place.  `info` is
+    the call's info struct (it has delivered and pending) and `fields` what
+    of it the caller gets (None: its scalar fields), `dtype` the record,
+    `align` what a DEVICE buffer of them needs, `noun` the name of the room
+    argument.  A code in `survivable` is not raised: the call did everything
+    else, and the info dict carries it as "status" (only such streams have
+    the key).  `call` is a closure (records, room, info) -> code; `check`
+    raises for a code (RaftEngine._check)."""
+
+    def __init__(self, info, dtype, align: int, noun: str, fields=None, survivable=()):
+        self.info, self.dtype, self.align, self.noun = info, dtype, align, noun
+        self.fields, self.survivable = fields, tuple(survivable)
+
+    def once(self, check, label: str, call, out_ptr, room) -> dict:
+        """One call; a null out_ptr (with room 0) is a peek, which stores nothing."""
+        info = self.info()
+        rc = call(C.c_void_p(out_ptr or 0), int(room), C.byref(info))
+        if rc not in self.survivable:
+            check(rc, label)
+        d = abi.info_dict(info, self.fields)
+        if self.survivable:
+            d["status"] = int(rc)
+        return d
+
+    def host(self, check, what: str, call, room, peek: bool = False, label: str | None = None):
+        """(info, records) into a numpy array of at most `room` records (None:
+        as many as there are -- a peek sizes the buffer); peek=True: the peek
+        alone and no record."""
+        _int(what, self.noun, room, lo=0, allow_none=True)
+        label = label or what
+        if peek:
+            return self.once(check, label, call, 0, 0), np.zeros(0, dtype=self.dtype)
+        if room is None:
+            room = self.once(check, label, call, 0, 0)["pending"]
+        # room 0 with a buffer is a call like any other (it stores what a delivery stores), not a peek: never a
+        # null buffer
+        out = np.zeros(max(1, int(room)), dtype=self.dtype)
+        info = self.once(check, label, call, out.ctypes.data, room)
+        return info, out[: info["delivered"]]
+
+    def dev(self, check, what: str, call, out_ptr, room, after_stream=None, wait=None, label: str | None = None) -> dict:
+        """The info of one call into a DEVICE buffer of `room` records."""
+        _int(what, self.noun, room, lo=0, allow_none=True)
+        if room is None or (room > 0 and not out_ptr):
+            raise ValueError(f"{what}: a device buffer and its {self.noun} are required")
+        _dev_prologue(what, {"record": out_ptr}, self.align, after_stream, wait)
+        return self.once(check, label or what, call, out_ptr, room)
+
+
+_DRAIN = _RecordStream(abi.raft_drain_info, abi.APPLIED_DTYPE, 8, "max_entries", survivable=(abi.RAFT_EWINDOW,))
+_WATCH = _RecordStream(abi.raft_watch_info, abi.EVENT_DTYPE, 8, "max_events")
+_ISOLATED = _RecordStream(abi.raft_isolated_info, abi.ISOLATED_DTYPE, 16, "max_events")
+_AUDIT_REPORT = _RecordStream(abi.raft_audit_report_info, abi.AUDIT_EVENT_DTYPE, 16, "max_events")
+_MONITOR_REPORT = _RecordStream(abi.raft_monitor_report_info, abi.MONITOR_EVENT_DTYPE, 16, "max_events")
+_WAL = _RecordStream(abi.raft_wal_info, abi.WAL_RECORD_DTYPE, 8, "max_records", survivable=(abi.RAFT_EWINDOW,))
+
+
 class RaftComm:
     """An RCCL communicator for the counter all-reduce of a sharded run
     (include/raft_engine.h raft_comm_*): rank 0 makes `unique_id()`, every
@@ -63,13 +163,35 @@ class RaftComm:
 
 class _GroupLedger:
     """What the handles that keep a ledger per group beside an engine share
-    (RaftAudit, RaftMonitor, RaftWal): the error check, the group-range and max_events
-    arguments, and closing on exit or collection.  A subclass sets _lib, _h and
-    G and has close()."""
+    (RaftAudit, RaftMonitor, RaftWal): creating and closing the handle of the
+    C functions named `_prefix`_*, device_bytes and reset, the group-range
+    argument, the record stream, the ledgers as an int32 matrix, and closing
+    on exit or collection."""
+
+    _prefix = ""                                     # "raft_audit": the handle's functions are raft_audit_*
+
+    def __init__(self, engine: "RaftEngine"):
+        self._open(engine)
+
+    def _fn(self, name: str):
+        return getattr(self._lib, f"{self._prefix}_{name}")
+
+    def _open(self, engine: "RaftEngine", *config):
+        """`_prefix`_create(engine, *config, &handle)."""
+        self._lib, self.engine = engine._lib, engine
+        self.R, self.G = engine.R, engine.G
+        h = C.c_void_p()
+        engine._check(self._fn("create")(engine._h, *config, C.byref(h)), f"{self._prefix}_create")
+        self._h = h
 
     def _check(self, rc: int, what: str):
         if rc != abi.RAFT_OK:
             raise RaftError(f"{what} failed ({rc}): " + self._lib.raft_last_error().decode(errors="replace"))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)                              # (RaftEngine.close closes its handles first)
+            self._h = None
 
     def __del__(self):
         try:
@@ -83,18 +205,48 @@ class _GroupLedger:
     def __exit__(self, *a):
         self.close()
 
-    def _range(self, g0, n, what: str):
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
-        return int(g0), int(n)
+    @property
+    def device_bytes(self) -> int:
+        """HBM owned by the handle (RaftEngine.device_bytes does not count it)."""
+        return int(self._fn("device_bytes")(self._h))
 
-    @staticmethod
-    def _room(max_events, what: str):
-        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
-                                       or max_events < 0):
-            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
+    def reset(self):
+        """Back to the state as created: every ledger zero (a monitor's
+        availability totals too), every cursor of a persistence stream fresh
+        (its next poll sends everything)."""
+        self._check(self._fn("reset")(self._h), f"{self._prefix[5:]} reset")
+
+    def _range(self, g0, n, what: str):
+        return _span(what, self.G, g0, n)
+
+    def _observe(self, g0, n, info) -> dict:
+        g0, n = self._range(g0, n, "observe")
+        self._check(self._fn("observe")(self._h, g0, n, C.byref(info)), f"{self._prefix}_observe")
+        return abi.info_dict(info)
+
+    def _records(self, stream: _RecordStream, what: str, entry: str, args, room, dev: bool = False, out_ptr=None):
+        """The handle's record stream `entry` (report, poll) with the call's
+        leading arguments `args`: stream.host, or with dev=True stream.dev
+        into out_ptr."""
+        name = f"{self._prefix}_{entry}_dev" if dev else f"{self._prefix}_{entry}"
+        call = _stream_call(self, name, *args)
+        if dev:
+            return stream.dev(self._check, what, call, out_ptr, room, label=name)
+        return stream.host(self._check, what, call, room, label=name)
+
+    def _read_words(self, g0, n) -> np.ndarray:
+        n = self.G - g0 if n is None else n
+        out = np.zeros((max(int(n), 0), self.words), dtype=np.int32)   # a bad range is the library's to refuse
+        self._check(self._fn("read")(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), f"{self._prefix}_read")
+        return out
+
+    def _write_words(self, ledger, g0):
+        a = np.asarray(ledger)
+        if a.ndim != 2 or a.shape[1] != self.words or a.dtype.kind not in "iu":
+            raise ValueError(f"{self._prefix[5:]} write: ledger {a.shape} {a.dtype} must be an integer array of shape "
+                             f"(n, {self.words})")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        self._check(self._fn("write")(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), f"{self._prefix}_write")
 
 
 class RaftAudit(_GroupLedger):
@@ -105,42 +257,18 @@ class RaftAudit(_GroupLedger):
     leader that lacks it.  Made by RaftEngine.audit(); close it before its
     engine.  RaftEngine.reset does not reach it: call reset() here."""
 
+    _prefix = "raft_audit"
+
     def __init__(self, engine: "RaftEngine"):
-        self._lib, self.engine = engine._lib, engine
-        self.R, self.G = engine.R, engine.G
+        self._open(engine)
         self.words = abi.audit_words(self.R)
-        h = C.c_void_p()
-        engine._check(self._lib.raft_audit_create(engine._h, C.byref(h)), "raft_audit_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.raft_audit_destroy(self._h)                     # (RaftEngine.close closes its audits first)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        """HBM owned by the audit (RaftEngine.device_bytes does not count it)."""
-        return int(self._lib.raft_audit_device_bytes(self._h))
-
-    def reset(self):
-        """Every ledger back to its zero state (as created)."""
-        self._check(self._lib.raft_audit_reset(self._h), "audit reset")
 
     def observe(self, g0: int = 0, n: int | None = None) -> dict:
         """raft_audit_observe of groups [g0, g0 + n): check the state now
         against the ledger and advance the ledger.  Returns newly_flagged,
         flagged, one count per kind (abi.AUDIT_KINDS) of the groups that gained
         that bit in this call, and unknown (checks skipped below a log_window)."""
-        g0, n = self._range(g0, n, "observe")
-        ai = abi.raft_audit_info()
-        self._check(self._lib.raft_audit_observe(self._h, g0, n, C.byref(ai)), "raft_audit_observe")
-        return {k: int(getattr(ai, k)) for k in abi.AUDIT_INFO_FIELDS}
-
-    def _report(self, fn, g0, n, out_ptr, room, what: str) -> dict:
-        ri = abi.raft_audit_report_info()
-        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(ri)), what)
-        return {k: int(getattr(ri, k)) for k in abi.AUDIT_REPORT_FIELDS}
+        return self._observe(g0, n, abi.raft_audit_info())
 
     def report(self, g0: int = 0, n: int | None = None, max_events: int | None = None):
         """raft_audit_report: (info, events) -- the groups of [g0, g0 + n) with
@@ -148,45 +276,25 @@ class RaftAudit(_GroupLedger):
         first_step) in ascending group order, at most max_events of them (None:
         all of them; 0: a peek).  info: delivered, pending, flagged.  Nothing
         is consumed: the same call returns the same events."""
-        g0, n = self._range(g0, n, "report")
-        self._room(max_events, "report")
-        fn = self._lib.raft_audit_report
-        if max_events is None:
-            max_events = self._report(fn, g0, n, 0, 0, "raft_audit_report")["pending"]
-        out = np.zeros(max(1, int(max_events)), dtype=abi.AUDIT_EVENT_DTYPE)
-        info = self._report(fn, g0, n, out.ctypes.data, int(max_events), "raft_audit_report")
-        return info, out[: info["delivered"]]
+        return self._records(_AUDIT_REPORT, "report", "report", self._range(g0, n, "report"), max_events)
 
     def report_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None) -> dict:
         """report into a DEVICE buffer of max_events 16-byte records (16-byte
         aligned); returns the info once the kernels finished."""
-        g0, n = self._range(g0, n, "report_dev")
-        self._room(max_events, "report_dev")
-        if max_events is None or (max_events > 0 and not out_ptr):
-            raise ValueError("report_dev: a device buffer and its max_events are required")
-        if out_ptr % 16:
-            raise ValueError("report_dev: the record buffer must be 16-byte aligned")
-        return self._report(self._lib.raft_audit_report_dev, g0, n, out_ptr, max_events, "raft_audit_report_dev")
+        return self._records(_AUDIT_REPORT, "report_dev", "report", self._range(g0, n, "report_dev"), max_events, True,
+                             out_ptr)
 
     def read(self, g0: int = 0, n: int | None = None) -> np.ndarray:
         """The ledgers of groups [g0, g0 + n): [n, 8 + 2 R] int32 (abi.AUDIT_WORDS,
         then (currentTerm, votedFor) per replica)."""
-        n = self.G - g0 if n is None else n
-        out = np.zeros((max(int(n), 0), self.words), dtype=np.int32)   # a bad range is the library's to refuse
-        self._check(self._lib.raft_audit_read(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "raft_audit_read")
-        return out
+        return self._read_words(g0, n)
 
     def write(self, ledger: np.ndarray, g0: int = 0):
         """Store the ledgers of groups [g0, g0 + len(ledger)) (resuming an
         audit): an integer [n, 8 + 2 R] array.  The library refuses unknown flag
         bits, a lead_replica outside -1..R-1 and an anchor_count outside
         0..log_cap, and stores nothing then."""
-        a = np.asarray(ledger)
-        if a.ndim != 2 or a.shape[1] != self.words or a.dtype.kind not in "iu":
-            raise ValueError(f"audit write: ledger {a.shape} {a.dtype} must be an integer array of shape "
-                             f"(n, {self.words})")
-        a = np.ascontiguousarray(a, dtype=np.int32)
-        self._check(self._lib.raft_audit_write(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)), "raft_audit_write")
+        self._write_words(ledger, g0)
 
 
 class RaftMonitor(_GroupLedger):
@@ -198,35 +306,17 @@ class RaftMonitor(_GroupLedger):
     ended.  Made by RaftEngine.monitor(); close it before its engine.
     RaftEngine.reset does not reach it: call reset() here."""
 
+    _prefix = "raft_monitor"
+    words = abi.MONITOR_WORDS
+
     def __init__(self, engine: "RaftEngine", **thresholds):
-        self._lib, self.engine = engine._lib, engine
-        self.R, self.G = engine.R, engine.G
-        self.words = abi.MONITOR_WORDS
         cfg = abi.raft_monitor_config()
         for k, v in thresholds.items():
             if k not in abi.MONITOR_CONFIG_FIELDS:
                 raise TypeError(f"monitor: unknown threshold {k!r}")
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 31:
-                raise ValueError(f"monitor: {k} must be an integer in 0..2^31-1, not {v!r}")
-            setattr(cfg, k, int(v))
-        self.config = {k: int(getattr(cfg, k)) for k in abi.MONITOR_CONFIG_FIELDS}
-        h = C.c_void_p()
-        engine._check(self._lib.raft_monitor_create(engine._h, C.byref(cfg), C.byref(h)), "raft_monitor_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.raft_monitor_destroy(self._h)                   # (RaftEngine.close closes its monitors first)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        """HBM owned by the monitor (RaftEngine.device_bytes does not count it)."""
-        return int(self._lib.raft_monitor_device_bytes(self._h))
-
-    def reset(self):
-        """Every ledger and the availability totals back to their zero state (as created)."""
-        self._check(self._lib.raft_monitor_reset(self._h), "monitor reset")
+            setattr(cfg, k, _int("monitor", k, v, 0, 2 ** 31 - 1))
+        self.config = abi.info_dict(cfg)
+        self._open(engine, C.byref(cfg))
 
     def observe(self, g0: int = 0, n: int | None = None) -> dict:
         """raft_monitor_observe of groups [g0, g0 + n): bring their ledgers up
@@ -234,21 +324,13 @@ class RaftMonitor(_GroupLedger):
         one count per kind (abi.MONITOR_KINDS) of the groups that carry the bit
         now, down (groups without a leader, flagged or not yet), and the
         outages that ended in this call with the sum of their lengths."""
-        g0, n = self._range(g0, n, "observe")
-        mi = abi.raft_monitor_info()
-        self._check(self._lib.raft_monitor_observe(self._h, g0, n, C.byref(mi)), "raft_monitor_observe")
-        return {k: int(getattr(mi, k)) for k in abi.MONITOR_INFO_FIELDS}
+        return self._observe(g0, n, abi.raft_monitor_info())
 
-    def _which(self, ever: bool, kinds, what: str):
-        kinds = abi.MONITOR_ALL if kinds is None else kinds
-        if isinstance(kinds, bool) or not isinstance(kinds, (int, np.integer)) or kinds & ~abi.MONITOR_ALL:
-            raise ValueError(f"{what}: kinds must be None or an OR of abi.MONITOR_* bits, not {kinds!r}")
-        return abi.MONITOR_EVER if ever else abi.MONITOR_NOW, int(kinds)
-
-    def _report(self, fn, g0, n, which, kinds, out_ptr, room, what: str) -> dict:
-        ri = abi.raft_monitor_report_info()
-        self._check(fn(self._h, g0, n, which, kinds, C.c_void_p(out_ptr or 0), int(room), C.byref(ri)), what)
-        return {k: int(getattr(ri, k)) for k in abi.MONITOR_REPORT_FIELDS}
+    def _selection(self, g0, n, ever: bool, kinds, what: str):
+        """(g0, n, which word, kinds): the leading arguments of a report."""
+        kinds = _int(what, "kinds", abi.MONITOR_ALL if kinds is None else kinds, 0, abi.MONITOR_ALL,
+                     want="None or an OR of abi.MONITOR_* bits")
+        return (*self._range(g0, n, what), abi.MONITOR_EVER if ever else abi.MONITOR_NOW, kinds)
 
     def report(self, g0: int = 0, n: int | None = None, max_events: int | None = None, *, ever: bool = False,
                kinds: int | None = None):
@@ -258,36 +340,22 @@ class RaftMonitor(_GroupLedger):
         now, ever, down_since, stall_since, leader, lag_mask) in ascending group
         order, at most max_events of them (None: all of them; 0: a peek).  info:
         delivered, pending, flagged.  Nothing is consumed."""
-        g0, n = self._range(g0, n, "report")
-        self._room(max_events, "report")
-        which, kinds = self._which(ever, kinds, "report")
-        fn = self._lib.raft_monitor_report
-        if max_events is None:
-            max_events = self._report(fn, g0, n, which, kinds, 0, 0, "raft_monitor_report")["pending"]
-        out = np.zeros(max(1, int(max_events)), dtype=abi.MONITOR_EVENT_DTYPE)
-        info = self._report(fn, g0, n, which, kinds, out.ctypes.data, int(max_events), "raft_monitor_report")
-        return info, out[: info["delivered"]]
+        return self._records(_MONITOR_REPORT, "report", "report", self._selection(g0, n, ever, kinds, "report"),
+                             max_events)
 
     def report_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None, *, ever: bool = False,
                    kinds: int | None = None) -> dict:
         """report into a DEVICE buffer of max_events 32-byte records (16-byte
         aligned); returns the info once the kernels finished."""
-        g0, n = self._range(g0, n, "report_dev")
-        self._room(max_events, "report_dev")
-        which, kinds = self._which(ever, kinds, "report_dev")
-        if max_events is None or (max_events > 0 and not out_ptr):
-            raise ValueError("report_dev: a device buffer and its max_events are required")
-        if out_ptr % 16:
-            raise ValueError("report_dev: the record buffer must be 16-byte aligned")
-        return self._report(self._lib.raft_monitor_report_dev, g0, n, which, kinds, out_ptr, max_events,
-                            "raft_monitor_report_dev")
+        return self._records(_MONITOR_REPORT, "report_dev", "report",
+                             self._selection(g0, n, ever, kinds, "report_dev"), max_events, True, out_ptr)
 
     def availability(self) -> dict:
         """raft_monitor_get_availability: hist ([32] int64; hist[k] counts the
         ended outages of 2^k .. 2^(k+1) - 1 steps), outages, down_steps."""
         av = abi.raft_monitor_availability()
         self._check(self._lib.raft_monitor_get_availability(self._h, C.byref(av)), "raft_monitor_get_availability")
-        return {"hist": np.array(av.hist[:], dtype=np.int64), "outages": int(av.outages), "down_steps": int(av.down_steps)}
+        return {"hist": np.array(av.hist[:], dtype=np.int64), **abi.info_dict(av)}
 
     def set_availability(self, hist, outages: int, down_steps: int):
         """raft_monitor_set_availability (resuming a monitor): the library
@@ -302,23 +370,14 @@ class RaftMonitor(_GroupLedger):
 
     def read(self, g0: int = 0, n: int | None = None) -> np.ndarray:
         """The ledgers of groups [g0, g0 + n): [n, 16] int32 (abi.MONITOR_WORD_NAMES)."""
-        n = self.G - g0 if n is None else n
-        out = np.zeros((max(int(n), 0), self.words), dtype=np.int32)   # a bad range is the library's to refuse
-        self._check(self._lib.raft_monitor_read(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "raft_monitor_read")
-        return out
+        return self._read_words(g0, n)
 
     def write(self, ledger: np.ndarray, g0: int = 0):
         """Store the ledgers of groups [g0, g0 + len(ledger)) (resuming a
         monitor): an integer [n, 16] array.  The library refuses unknown bits in
         now or ever, a leader outside -1..R-1, lag_mask bits at or above R, a
         negative count and nonzero reserved words, and stores nothing then."""
-        a = np.asarray(ledger)
-        if a.ndim != 2 or a.shape[1] != self.words or a.dtype.kind not in "iu":
-            raise ValueError(f"monitor write: ledger {a.shape} {a.dtype} must be an integer array of shape "
-                             f"(n, {self.words})")
-        a = np.ascontiguousarray(a, dtype=np.int32)
-        self._check(self._lib.raft_monitor_write(self._h, int(g0), a.shape[0], abi.ptr(a, C.c_int32)),
-                    "raft_monitor_write")
+        self._write_words(ledger, g0)
 
 
 class RaftWal(_GroupLedger):
@@ -330,51 +389,18 @@ class RaftWal(_GroupLedger):
     Made by RaftEngine.wal(); close it before its engine.  RaftEngine.reset
     does not reach it: call reset() here."""
 
-    def __init__(self, engine: "RaftEngine"):
-        self._lib, self.engine = engine._lib, engine
-        self.R, self.G = engine.R, engine.G
-        h = C.c_void_p()
-        engine._check(self._lib.raft_wal_create(engine._h, C.byref(h)), "raft_wal_create")
-        self._h = h
+    _prefix = "raft_wal"
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.raft_wal_destroy(self._h)                       # (RaftEngine.close closes its wals first)
-            self._h = None
-
-    @property
-    def device_bytes(self) -> int:
-        """HBM owned by the stream (RaftEngine.device_bytes does not count it)."""
-        return int(self._lib.raft_wal_device_bytes(self._h))
-
-    def reset(self):
-        """Every cursor fresh (as created): the next poll sends everything."""
-        self._check(self._lib.raft_wal_reset(self._h), "wal reset")
-
-    def _args(self, g0, n, replica, max_records, what: str):
-        g0, n = self._range(g0, n, what)
-        if not isinstance(replica, (int, np.integer)) or isinstance(replica, bool) or not -1 <= replica < self.R:
-            raise ValueError(f"{what}: replica {replica!r} must be -1 (all) or in 0..{self.R - 1}")
-        if max_records is not None and (not isinstance(max_records, (int, np.integer)) or isinstance(max_records, bool)
-                                        or max_records < 0):
-            raise ValueError(f"{what}: max_records must be None or an integer >= 0, not {max_records!r}")
-        return g0, n, int(replica)
-
-    def _poll(self, fn, g0, n, replica, out_ptr, room, what: str) -> dict:
-        """One poll.  RAFT_EWINDOW is not raised: the call did everything else,
-        so info["status"] carries the code (info["lost"] > 0 says how many
-        entries left the log window unread)."""
-        wi = abi.raft_wal_info()
-        rc = fn(self._h, g0, n, replica, C.c_void_p(out_ptr or 0), int(room), C.byref(wi))
-        if rc != abi.RAFT_EWINDOW:
-            self._check(rc, what)
-        return {**{k: int(getattr(wi, k)) for k in abi.WAL_INFO_FIELDS}, "status": int(rc)}
+    def _selection(self, g0, n, replica, what: str):
+        """(g0, n, replica): the leading arguments of a poll."""
+        return (*self._range(g0, n, what),
+                _int(what, "replica", replica, -1, self.R - 1, want=f"-1 (all) or in 0..{self.R - 1}"))
 
     def peek(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
         """What a poll would see, storing nothing: info with delivered = 0 and
         pending = every record of the selection."""
-        g0, n, replica = self._args(g0, n, replica, None, "peek")
-        return self._poll(self._lib.raft_wal_poll, g0, n, replica, 0, 0, "raft_wal_poll")
+        call = _stream_call(self, "raft_wal_poll", *self._selection(g0, n, replica, "peek"))
+        return _WAL.once(self._check, "raft_wal_poll", call, 0, 0)
 
     def poll(self, g0: int = 0, n: int | None = None, replica: int = -1, max_records: int | None = None):
         """raft_wal_poll of groups [g0, g0 + n) (replica -1: every replica, else
@@ -384,24 +410,17 @@ class RaftWal(_GroupLedger):
         ascending inside a replica; at most max_records of them (None: as many
         as there are -- a peek sizes the buffer).  The cursors advance past
         what was returned.  info: delivered, pending, hardstates, truncates,
-        entries, lost, regressed, status."""
-        g0, n, replica = self._args(g0, n, replica, max_records, "poll")
-        if max_records is None:
-            max_records = self.peek(g0, n, replica)["pending"]
-        # room 0 with a buffer is a poll (the floors move), not a peek: never a null buffer
-        out = np.zeros(max(1, int(max_records)), dtype=abi.WAL_RECORD_DTYPE)
-        info = self._poll(self._lib.raft_wal_poll, g0, n, replica, out.ctypes.data, int(max_records), "raft_wal_poll")
-        return out[: info["delivered"]], info
+        entries, lost, regressed, status: RAFT_EWINDOW is not raised, the call
+        did everything else (info["lost"] > 0 says how many entries left the
+        log window unread)."""
+        info, records = self._records(_WAL, "poll", "poll", self._selection(g0, n, replica, "poll"), max_records)
+        return records, info
 
     def poll_dev(self, out_ptr: int, max_records: int, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
         """poll into a DEVICE buffer of max_records 24-byte records (8-byte
         aligned); returns the info once the kernels finished."""
-        g0, n, replica = self._args(g0, n, replica, max_records, "poll_dev")
-        if max_records is None or (max_records > 0 and not out_ptr):
-            raise ValueError("poll_dev: a device buffer and its max_records are required")
-        if out_ptr % 8:
-            raise ValueError("poll_dev: the record buffer must be 8-byte aligned")
-        return self._poll(self._lib.raft_wal_poll_dev, g0, n, replica, out_ptr, max_records, "raft_wal_poll_dev")
+        return self._records(_WAL, "poll_dev", "poll", self._selection(g0, n, replica, "poll_dev"), max_records, True,
+                             out_ptr)
 
     def cursors(self, g0: int = 0, n: int | None = None) -> np.ndarray:
         """The cursors of groups [g0, g0 + n): [n, R] of abi.WAL_CURSOR_DTYPE
@@ -493,13 +512,18 @@ class RaftEngine:
             msg = self._lib.raft_last_error().decode(errors="replace")
             raise RaftError(f"{what} failed ({rc}): {msg}")
 
+    def _adopt(self, child):
+        """Remember a handle made from this engine (an audit, a monitor, a
+        persistence stream), weakly: close() closes it first."""
+        self.__dict__.setdefault("_children", []).append(weakref.ref(child))
+        return child
+
     def close(self):
         if getattr(self, "_h", None):
-            for ref in (*getattr(self, "_audits", ()), *getattr(self, "_monitors", ()),   # they go before their engine
-                        *getattr(self, "_wals", ())):
-                a = ref()
-                if a is not None:
-                    a.close()
+            for ref in getattr(self, "_children", ()):                # they go before their engine
+                child = ref()
+                if child is not None:
+                    child.close()
             self._lib.raft_engine_destroy(self._h)
             self._h = None
 
@@ -514,6 +538,26 @@ class RaftEngine:
 
     def __exit__(self, *a):
         self.close()
+
+    def _dev(self, what: str, after_stream, align: int = 16, **ptrs):
+        """The prologue of a call on DEVICE pointers: the alignment of the
+        named buffers, then `after_stream`."""
+        _dev_prologue(what, ptrs, align, after_stream, self.wait_stream)
+
+    def _records_dev(self, stream: _RecordStream, what: str, name: str, args, out_ptr, room, after_stream) -> dict:
+        return stream.dev(self._check, what, _stream_call(self, name, *args), out_ptr, room, after_stream, self.wait_stream)
+
+    @staticmethod
+    def _byte_mask(mask, n, what: str):
+        """A mask of one byte per group as (contiguous uint8 array, n): the C
+        side reads n bytes."""
+        m = np.asarray(mask)
+        if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
+            raise ValueError(f"{what}: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
+        n = m.shape[0] if n is None else n
+        if m.shape[0] != n:
+            raise ValueError(f"{what}: mask holds {m.shape[0]} groups, n is {n}")
+        return np.ascontiguousarray(m, dtype=np.uint8), n
 
     @property
     def stream(self) -> int:
@@ -573,7 +617,7 @@ class RaftEngine:
         balanced schedule), subranges."""
         k = abi.raft_kernel_info()
         self._check(self._lib.raft_engine_kernel_info(self._h, C.byref(k)), "kernel_info")
-        return {n: int(getattr(k, n)) for n, _ in abi.raft_kernel_info._fields_ if n != "reserved"}
+        return abi.info_dict(k)
 
     @property
     def device_bytes(self) -> int:
@@ -663,34 +707,17 @@ class RaftEngine:
         return (int(out.value), f) if flags else int(out.value)
 
     # -- committed-entry delivery (lastApplied, RaftServer.kt:47) ------------
-    def _drain_args(self, g0, n, replica, max_entries, what: str):
-        """The drain's arguments, checked before any library call."""
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n), ("replica", replica)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
-        if not -1 <= replica < self.R:
-            raise ValueError(f"{what}: replica {replica} must be -1 (all) or in 0..{self.R - 1}")
-        if max_entries is not None and (not isinstance(max_entries, (int, np.integer)) or max_entries < 0):
-            raise ValueError(f"{what}: max_entries must be None or an integer >= 0, not {max_entries!r}")
-        return int(g0), int(n), int(replica)
-
-    def _drain(self, fn, g0, n, replica, out_ptr, room, what: str) -> dict:
-        """One drain call.  RAFT_EWINDOW is not raised: the call did everything
-        else, so the records are returned and info["status"] carries the code
-        (info["lost"] > 0 says how many entries left the log window unread)."""
-        di = abi.raft_drain_info()
-        rc = fn(self._h, g0, n, replica, C.c_void_p(out_ptr or 0), int(room), C.byref(di))
-        if rc != abi.RAFT_EWINDOW:
-            self._check(rc, what)
-        return {"delivered": int(di.delivered), "pending": int(di.pending), "lost": int(di.lost),
-                "regressed": int(di.regressed), "status": int(rc)}
+    def _replica_span(self, g0, n, replica, what: str):
+        """(g0, n, replica) of a call on one replica index or all (-1), checked
+        before any library call."""
+        g0, n = _span(what, self.G, g0, n)
+        return g0, n, _int(what, "replica", replica, -1, self.R - 1, want=f"-1 (all) or in 0..{self.R - 1}")
 
     def peek_committed(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
         """What a drain would see, storing nothing: info with delivered = 0 and
         pending = every committed, undelivered entry of the selection."""
-        g0, n, replica = self._drain_args(g0, n, replica, None, "peek_committed")
-        return self._drain(self._lib.raft_engine_drain_committed, g0, n, replica, 0, 0, "peek_committed")
+        call = _stream_call(self, "raft_engine_drain_committed", *self._replica_span(g0, n, replica, "peek_committed"))
+        return _DRAIN.once(self._check, "peek_committed", call, 0, 0)
 
     def drain_committed(self, g0: int = 0, n: int | None = None, replica: int = -1,
                         max_entries: int | None = None):
@@ -700,36 +727,28 @@ class RaftEngine:
         replica, index, term, cmd) in ascending (group, replica, index) order,
         at most max_entries of them (None: as many as there are -- a peek sizes
         the buffer); lastApplied advances past what was returned.  info:
-        delivered, pending, lost, regressed, status (include/raft_engine.h)."""
-        g0, n, replica = self._drain_args(g0, n, replica, max_entries, "drain_committed")
-        if max_entries is None:
-            max_entries = self.peek_committed(g0, n, replica)["pending"]
-        # room 0 with a buffer is a drain (it stores the ring skip), not a peek: never a null buffer
-        out = np.zeros(max(1, int(max_entries)), dtype=abi.APPLIED_DTYPE)
-        info = self._drain(self._lib.raft_engine_drain_committed, g0, n, replica, out.ctypes.data, int(max_entries),
-                           "drain_committed")
-        return out[: info["delivered"]], info
+        delivered, pending, lost, regressed, status (include/raft_engine.h):
+        RAFT_EWINDOW is not raised, the call did everything else and the
+        records are returned (info["lost"] > 0 says how many entries left the
+        log window unread)."""
+        call = _stream_call(self, "raft_engine_drain_committed", *self._replica_span(g0, n, replica, "drain_committed"))
+        info, records = _DRAIN.host(self._check, "drain_committed", call, max_entries)
+        return records, info
 
     def drain_committed_dev(self, out_ptr: int, max_entries: int, g0: int = 0, n: int | None = None,
                             replica: int = -1, after_stream: int | None = None) -> dict:
         """drain_committed into a DEVICE buffer of max_entries 24-byte records
         (e.g. a torch uint8 tensor's data_ptr() on this engine's GPU; 8-byte
         aligned); returns info once the kernels finished."""
-        g0, n, replica = self._drain_args(g0, n, replica, max_entries, "drain_committed_dev")
-        if max_entries is None or (max_entries > 0 and not out_ptr):
-            raise ValueError("drain_committed_dev: a device buffer and its max_entries are required")
-        if out_ptr % 8:
-            raise ValueError("drain_committed_dev: the record buffer must be 8-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
-        return self._drain(self._lib.raft_engine_drain_committed_dev, g0, n, replica, out_ptr, max_entries,
-                           "drain_committed_dev")
+        return self._records_dev(_DRAIN, "drain_committed_dev", "raft_engine_drain_committed_dev",
+                                 self._replica_span(g0, n, replica, "drain_committed_dev"), out_ptr, max_entries,
+                                 after_stream)
 
     def applied(self, g0: int = 0, n: int | None = None) -> np.ndarray:
         """lastApplied of groups [g0, g0 + n): [n, R] int32."""
         n = self.G - g0 if n is None else n
-        out = np.zeros((max(n, 0), self.R), dtype=np.int32)          # a bad range is the library's to refuse
-        self._check(self._lib.raft_engine_read_applied(self._h, g0, n, abi.ptr(out, C.c_int32)), "read_applied")
+        out = np.zeros((max(int(n), 0), self.R), dtype=np.int32)     # a bad range is the library's to refuse
+        self._check(self._lib.raft_engine_read_applied(self._h, int(g0), int(n), abi.ptr(out, C.c_int32)), "read_applied")
         return out
 
     def set_applied(self, applied: np.ndarray, g0: int = 0):
@@ -789,10 +808,7 @@ class RaftEngine:
         """raft_propose_batch_dev: DEVICE pointers to n int64 groups, uint32
         commands and 16-byte tickets (16-byte aligned); returns RAFT_OK or
         RAFT_EWINDOW once the batch finished."""
-        if ticket_ptr % 16:
-            raise ValueError("propose_dev: the ticket buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("propose_dev", after_stream, ticket=ticket_ptr)
         return self._client_status(self._lib.raft_propose_batch_dev(self._h, group_ptr, cmd_ptr, ticket_ptr, int(n)),
                                    "raft_propose_batch_dev")
 
@@ -817,10 +833,7 @@ class RaftEngine:
                     after_stream: int | None = None) -> int:
         """raft_engine_resolve_tickets_dev on DEVICE pointers (tickets and
         records 16-byte aligned); returns RAFT_OK or RAFT_EWINDOW."""
-        if ticket_ptr % 16 or out_ptr % 16:
-            raise ValueError("resolve_dev: the ticket and record buffers must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("resolve_dev", after_stream, ticket=ticket_ptr, record=out_ptr)
         return self._client_status(self._lib.raft_engine_resolve_tickets_dev(self._h, group_ptr, ticket_ptr, cmd_ptr,
                                                                              out_ptr, int(n)),
                                    "raft_engine_resolve_tickets_dev")
@@ -844,10 +857,7 @@ class RaftEngine:
     def begin_reads_dev(self, group_ptr: int, ticket_ptr: int, n: int, after_stream: int | None = None) -> int:
         """raft_read_begin_batch_dev: DEVICE pointers to n int64 groups and
         16-byte tickets (16-byte aligned); returns RAFT_OK or RAFT_EWINDOW."""
-        if ticket_ptr % 16:
-            raise ValueError("begin_reads_dev: the ticket buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("begin_reads_dev", after_stream, ticket=ticket_ptr)
         return self._client_status(self._lib.raft_read_begin_batch_dev(self._h, group_ptr, ticket_ptr, int(n)),
                                    "raft_read_begin_batch_dev")
 
@@ -874,10 +884,7 @@ class RaftEngine:
                         after_stream: int | None = None, check: bool = True) -> int:
         """raft_read_serve_batch_dev on DEVICE pointers (tickets and records
         16-byte aligned); returns the call's code (see serve_reads)."""
-        if ticket_ptr % 16 or out_ptr % 16:
-            raise ValueError("serve_reads_dev: the ticket and record buffers must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("serve_reads_dev", after_stream, ticket=ticket_ptr, record=out_ptr)
         allowed = () if check or not self.sm_slots else (abi.RAFT_ERANGE, abi.RAFT_EINVAL)
         return self._client_status(self._lib.raft_read_serve_batch_dev(self._h, group_ptr, ticket_ptr, key_ptr, out_ptr,
                                                                        int(n)), "raft_read_serve_batch_dev", allowed)
@@ -891,10 +898,11 @@ class RaftEngine:
     def sm_configure(self, slots: int):
         """Allocate and zero the state machine with `slots` registers per
         replica (a power of two in 1..64; again: zero it or resize it); 0 frees it."""
-        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or (slots != 0 and slots not in abi.SM_SLOTS):
+        slots = _int("sm_configure", "slots", slots, want="0 or a power of two in 1..64")
+        if slots != 0 and slots not in abi.SM_SLOTS:
             raise ValueError(f"sm_configure: slots must be 0 or a power of two in 1..64, not {slots!r}")
-        self._check(self._lib.raft_engine_sm_configure(self._h, int(slots)), "sm_configure")
-        self._sm_slots = int(slots)
+        self._check(self._lib.raft_engine_sm_configure(self._h, slots), "sm_configure")
+        self._sm_slots = slots
 
     def sm_apply(self, g0: int = 0, n: int | None = None, replica: int = -1) -> dict:
         """Apply the entries of groups [g0, g0 + n) (replica -1: every replica,
@@ -902,12 +910,12 @@ class RaftEngine:
         cursor, on the device: info with applied, lost, regressed, status.
         RAFT_EWINDOW (entries left the log window unapplied) is not raised: the
         call did everything else and info["status"] carries the code."""
-        g0, n, replica = self._drain_args(g0, n, replica, None, "sm_apply")
+        g0, n, replica = self._replica_span(g0, n, replica, "sm_apply")
         si = abi.raft_sm_info()
         rc = self._lib.raft_engine_sm_apply(self._h, g0, n, replica, C.byref(si))
         if rc != abi.RAFT_EWINDOW:
             self._check(rc, "sm_apply")
-        return {"applied": int(si.applied), "lost": int(si.lost), "regressed": int(si.regressed), "status": int(rc)}
+        return {**abi.info_dict(si), "status": int(rc)}
 
     def sm_read(self, g0: int = 0, n: int | None = None, regs: bool = True):
         """The machines of groups [g0, g0 + n): (heads, regs) -- heads [n, R] of
@@ -982,18 +990,10 @@ class RaftEngine:
     # -- replica crash and restart (raft_engine_restart*) -------------------------
     def _restart_args(self, g0, n, amnesia, replay, down_steps, what: str):
         """The arguments every restart form shares, checked before any library call."""
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n), ("down_steps", down_steps)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
-        if not 0 <= down_steps <= abi.RESTART_MAX_DOWN_STEPS:
-            raise ValueError(f"{what}: down_steps must be in 0..{abi.RESTART_MAX_DOWN_STEPS}")
+        g0, n = _span(what, self.G, g0, n)
+        down_steps = _int(what, "down_steps", down_steps, 0, abi.RESTART_MAX_DOWN_STEPS)
         flags = (abi.RESTART_AMNESIA if amnesia else 0) | (abi.RESTART_REPLAY if replay else 0)
-        return int(g0), int(n), flags, int(down_steps)
-
-    @staticmethod
-    def _restart_info(ri: "abi.raft_restart_info") -> dict:
-        return {"restarted": int(ri.restarted), "leaders": int(ri.leaders), "entries_dropped": int(ri.entries_dropped)}
+        return g0, n, flags, down_steps
 
     def restart(self, mask=None, *, ppm: int | None = None, g0: int = 0, n: int | None = None,
                 amnesia: bool = False, replay: bool = False, down_steps: int = 0) -> dict:
@@ -1011,23 +1011,17 @@ class RaftEngine:
         if (mask is None) == (ppm is None):
             raise ValueError("restart: exactly one of mask and ppm is required")
         if mask is not None:
-            m = np.asarray(mask)
-            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
-                raise ValueError(f"restart: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
-            n = m.shape[0] if n is None else n
-            if m.shape[0] != n:
-                raise ValueError(f"restart: mask holds {m.shape[0]} groups, n is {n}")
-            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
-        elif not isinstance(ppm, (int, np.integer)) or isinstance(ppm, bool) or not 0 <= ppm <= 0xFFFFFFFF:
-            raise ValueError(f"restart: ppm must be an integer in 0..2^32-1, not {ppm!r}")
+            m, n = self._byte_mask(mask, n, "restart")
+        else:
+            ppm = _int("restart", "ppm", ppm, 0, 0xFFFFFFFF)
         g0, n, flags, down_steps = self._restart_args(g0, n, amnesia, replay, down_steps, "restart")
         ri = abi.raft_restart_info()
         if mask is not None:
             rc = self._lib.raft_engine_restart(self._h, g0, n, C.c_void_p(m.ctypes.data), flags, down_steps, C.byref(ri))
         else:
-            rc = self._lib.raft_engine_restart_random(self._h, g0, n, int(ppm), flags, down_steps, C.byref(ri))
+            rc = self._lib.raft_engine_restart_random(self._h, g0, n, ppm, flags, down_steps, C.byref(ri))
         self._check(rc, "raft_engine_restart" if mask is not None else "raft_engine_restart_random")
-        return self._restart_info(ri)
+        return abi.info_dict(ri)
 
     def restart_dev(self, mask_ptr: int, *, g0: int = 0, n: int | None = None, amnesia: bool = False,
                     replay: bool = False, down_steps: int = 0, after_stream: int | None = None) -> dict:
@@ -1036,12 +1030,11 @@ class RaftEngine:
         g0, n, flags, down_steps = self._restart_args(g0, n, amnesia, replay, down_steps, "restart_dev")
         if n > 0 and not mask_ptr:
             raise ValueError("restart_dev: a device mask is required")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("restart_dev", after_stream)
         ri = abi.raft_restart_info()
         self._check(self._lib.raft_engine_restart_dev(self._h, g0, n, C.c_void_p(mask_ptr or 0), flags, down_steps,
                                                       C.byref(ri)), "raft_engine_restart_dev")
-        return self._restart_info(ri)
+        return abi.info_dict(ri)
 
     # -- snapshot install (raft_engine_install_snapshot*) --------------------------
     def install_snapshot(self, mask=None, *, g0: int = 0, n: int | None = None, min_lag: int = 0,
@@ -1061,29 +1054,19 @@ class RaftEngine:
             raise ValueError("install_snapshot: at most one of mask and device_mask")
         m = None
         if mask is not None:
-            m = np.asarray(mask)
-            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
-                raise ValueError(f"install_snapshot: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
-            n = m.shape[0] if n is None else n
-            if m.shape[0] != n:
-                raise ValueError(f"install_snapshot: mask holds {m.shape[0]} groups, n is {n}")
-            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n), ("min_lag", min_lag)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"install_snapshot: {name} must be an integer, not {v!r}")
-        if min_lag < 0:
-            raise ValueError("install_snapshot: min_lag must not be negative")
+            m, n = self._byte_mask(mask, n, "install_snapshot")
+        g0, n = _span("install_snapshot", self.G, g0, n)
+        min_lag = _int("install_snapshot", "min_lag", min_lag, 0)
         ii = abi.raft_install_info()
         if device_mask is not None:
-            rc = self._lib.raft_engine_install_snapshot_dev(self._h, int(g0), int(n), C.c_void_p(int(device_mask)),
-                                                            int(min_lag), C.byref(ii))
+            rc = self._lib.raft_engine_install_snapshot_dev(self._h, g0, n, C.c_void_p(int(device_mask)), min_lag,
+                                                            C.byref(ii))
         else:
-            rc = self._lib.raft_engine_install_snapshot(self._h, int(g0), int(n),
+            rc = self._lib.raft_engine_install_snapshot(self._h, g0, n,
                                                         C.c_void_p(m.ctypes.data) if m is not None and m.size else None,
-                                                        int(min_lag), C.byref(ii))
+                                                        min_lag, C.byref(ii))
         self._check(rc, "raft_engine_install_snapshot")
-        return {k: int(getattr(ii, k)) for k in abi.INSTALL_INFO_FIELDS}
+        return abi.info_dict(ii)
 
     # -- leadership transfer (raft_transfer_batch*, raft_engine_resolve_transfers*, raft_engine_evacuate*) ----
     def transfer(self, groups, targets=None) -> np.ndarray:
@@ -1108,10 +1091,7 @@ class RaftEngine:
         """raft_transfer_batch_dev: DEVICE pointers to n int64 groups, int32
         targets and 16-byte tickets (16-byte aligned), e.g. torch tensors'
         data_ptr(); returns RAFT_OK once the batch finished."""
-        if ticket_ptr % 16:
-            raise ValueError("transfer_dev: the ticket buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("transfer_dev", after_stream, ticket=ticket_ptr)
         return self._client_status(self._lib.raft_transfer_batch_dev(self._h, group_ptr, target_ptr, ticket_ptr, int(n)),
                                    "raft_transfer_batch_dev", ())
 
@@ -1136,10 +1116,7 @@ class RaftEngine:
                               after_stream: int | None = None, check: bool = True) -> int:
         """raft_engine_resolve_transfers_dev on DEVICE pointers (tickets and
         records 16-byte aligned); returns the call's code (see resolve_transfers)."""
-        if ticket_ptr % 16 or out_ptr % 16:
-            raise ValueError("resolve_transfers_dev: the ticket and record buffers must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("resolve_transfers_dev", after_stream, ticket=ticket_ptr, record=out_ptr)
         return self._client_status(self._lib.raft_engine_resolve_transfers_dev(self._h, group_ptr, ticket_ptr, out_ptr,
                                                                                int(n)),
                                    "raft_engine_resolve_transfers_dev", () if check else (abi.RAFT_ERANGE, abi.RAFT_EINVAL))
@@ -1151,28 +1128,23 @@ class RaftEngine:
         after that leader, cyclically -- the step before a planned restart of
         the masked replicas.  Returns led, sent, no_target, behind, busy
         (include/raft_engine.h raft_evacuate_info)."""
-        m = np.asarray(mask)
-        if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
-            raise ValueError(f"evacuate: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
-        if not isinstance(g0, (int, np.integer)) or isinstance(g0, bool):
-            raise ValueError(f"evacuate: g0 must be an integer, not {g0!r}")
-        m = np.ascontiguousarray(m, dtype=np.uint8)                   # the C side reads n bytes
+        m, n = self._byte_mask(mask, None, "evacuate")
+        g0 = _int("evacuate", "g0", g0)
         ei = abi.raft_evacuate_info()
-        self._check(self._lib.raft_engine_evacuate(self._h, int(g0), m.shape[0], C.c_void_p(m.ctypes.data) if m.size else None,
+        self._check(self._lib.raft_engine_evacuate(self._h, g0, n, C.c_void_p(m.ctypes.data) if m.size else None,
                                                    C.byref(ei)), "raft_engine_evacuate")
-        return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
+        return abi.info_dict(ei)
 
     def evacuate_dev(self, mask_ptr: int, n: int, g0: int = 0, after_stream: int | None = None) -> dict:
         """evacuate with the mask in DEVICE memory (n bytes on this engine's GPU,
         e.g. a torch uint8 tensor's data_ptr()); returns once the kernel finished."""
         if n > 0 and not mask_ptr:
             raise ValueError("evacuate_dev: a device mask is required")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("evacuate_dev", after_stream)
         ei = abi.raft_evacuate_info()
         self._check(self._lib.raft_engine_evacuate_dev(self._h, int(g0), int(n), C.c_void_p(mask_ptr or 0), C.byref(ei)),
                     "raft_engine_evacuate_dev")
-        return {k: int(getattr(ei, k)) for k in abi.EVACUATE_INFO_FIELDS}
+        return abi.info_dict(ei)
 
     # -- scripted network faults (raft_isolate_batch*, raft_engine_heal_network*, raft_engine_list_isolated*) ----
     def isolate(self, groups, targets, steps, replace: bool = False) -> np.ndarray:
@@ -1206,10 +1178,7 @@ class RaftEngine:
         """raft_isolate_batch_dev: DEVICE pointers to n int64 groups, int32
         targets, int32 steps and 16-byte tickets (16-byte aligned), e.g. torch
         tensors' data_ptr(); returns RAFT_OK once the batch finished."""
-        if ticket_ptr % 16:
-            raise ValueError("isolate_dev: the ticket buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("isolate_dev", after_stream, ticket=ticket_ptr)
         return self._client_status(self._lib.raft_isolate_batch_dev(
             self._h, group_ptr, target_ptr, steps_ptr, abi.ISOLATE_REPLACE if replace else 0, ticket_ptr, int(n)),
             "raft_isolate_batch_dev", ())
@@ -1222,38 +1191,23 @@ class RaftEngine:
         (running, not selected)."""
         m = None
         if mask is not None:
-            m = np.asarray(mask)
-            if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (m.min() < 0 or m.max() > 0xFF)):
-                raise ValueError(f"heal_network: mask {m.shape} {m.dtype} must be a 1-D array of byte values")
-            n = m.shape[0] if n is None else n
-            if m.shape[0] != n:
-                raise ValueError(f"heal_network: mask holds {m.shape[0]} groups, n is {n}")
-            m = np.ascontiguousarray(m, dtype=np.uint8)               # the C side reads n bytes
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"heal_network: {name} must be an integer, not {v!r}")
+            m, n = self._byte_mask(mask, n, "heal_network")
+        g0, n = _span("heal_network", self.G, g0, n)
         hi = abi.raft_heal_info()
-        self._check(self._lib.raft_engine_heal_network(self._h, int(g0), int(n),
+        self._check(self._lib.raft_engine_heal_network(self._h, g0, n,
                                                        C.c_void_p(m.ctypes.data) if m is not None and m.size else None,
                                                        C.byref(hi)), "raft_engine_heal_network")
-        return {k: int(getattr(hi, k)) for k in abi.HEAL_INFO_FIELDS}
+        return abi.info_dict(hi)
 
     def heal_network_dev(self, mask_ptr: int, n: int, g0: int = 0, after_stream: int | None = None) -> dict:
         """heal_network with the mask in DEVICE memory (n bytes on this engine's
         GPU, e.g. a torch uint8 tensor's data_ptr(); 0: any replica); returns
         once the kernel finished."""
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("heal_network_dev", after_stream)
         hi = abi.raft_heal_info()
         self._check(self._lib.raft_engine_heal_network_dev(self._h, int(g0), int(n), C.c_void_p(mask_ptr or 0),
                                                            C.byref(hi)), "raft_engine_heal_network_dev")
-        return {k: int(getattr(hi, k)) for k in abi.HEAL_INFO_FIELDS}
-
-    def _list_isolated(self, fn, g0, n, out_ptr, room, what: str) -> dict:
-        ii = abi.raft_isolated_info()
-        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(ii)), what)
-        return {k: int(getattr(ii, k)) for k in abi.ISOLATED_INFO_FIELDS}
+        return abi.info_dict(hi)
 
     def isolated(self, g0: int = 0, n: int | None = None, max_events: int | None = None, peek: bool = False):
         """raft_engine_list_isolated: the groups of [g0, g0 + n) with a running
@@ -1262,38 +1216,19 @@ class RaftEngine:
         in ascending group order, at most max_events of them (None: as many as
         there are).  peek=True returns no record.  info: delivered, pending,
         running.  Read-only."""
-        g0, n = self._watch_args(g0, n, max_events, "isolated")
-        fn = self._lib.raft_engine_list_isolated
-        if peek:
-            return self._list_isolated(fn, g0, n, 0, 0, "isolated"), np.zeros(0, dtype=abi.ISOLATED_DTYPE)
-        if max_events is None:
-            max_events = self._list_isolated(fn, g0, n, 0, 0, "isolated")["pending"]
-        out = np.zeros(max(1, int(max_events)), dtype=abi.ISOLATED_DTYPE)   # never a null buffer: that would be a peek
-        info = self._list_isolated(fn, g0, n, out.ctypes.data, int(max_events), "isolated")
-        return info, out[: info["delivered"]]
+        call = _stream_call(self, "raft_engine_list_isolated", *_span("isolated", self.G, g0, n))
+        return _ISOLATED.host(self._check, "isolated", call, max_events, peek)
 
     def isolated_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None,
                      after_stream: int | None = None) -> dict:
         """isolated into a DEVICE buffer of max_events 16-byte records (16-byte
         aligned); returns the info once the kernels finished."""
-        g0, n = self._watch_args(g0, n, max_events, "isolated_dev")
-        if max_events is None or (max_events > 0 and not out_ptr):
-            raise ValueError("isolated_dev: a device buffer and its max_events are required")
-        if out_ptr % 16:
-            raise ValueError("isolated_dev: the record buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
-        return self._list_isolated(self._lib.raft_engine_list_isolated_dev, g0, n, out_ptr, max_events, "isolated_dev")
+        return self._records_dev(_ISOLATED, "isolated_dev", "raft_engine_list_isolated_dev",
+                                 _span("isolated_dev", self.G, g0, n), out_ptr, max_events, after_stream)
 
     # -- leader no-op entries (raft_engine_append_noops*, raft_engine_sm_set_noop) -------------------------
     def _noop_args(self, g0, n, cmd, what: str):
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n), ("cmd", cmd)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
-        if not 0 <= cmd <= 0xFFFFFFFF:
-            raise ValueError(f"{what}: cmd must be a u32 command id, not {cmd!r}")
-        return int(g0), int(n), int(cmd)
+        return (*_span(what, self.G, g0, n), _int(what, "cmd", cmd, 0, 0xFFFFFFFF, want="a u32 command id"))
 
     def append_noops(self, g0: int = 0, n: int | None = None, cmd: int = abi.NOOP_CMD, tickets: bool = False):
         """raft_engine_append_noops: in every group of [g0, g0 + n) whose newest
@@ -1314,7 +1249,7 @@ class RaftEngine:
         self._client_status(self._lib.raft_engine_append_noops(
             self._h, g0, n, cmd, C.c_void_p(t.ctypes.data) if tickets else None,
             C.c_void_p(c.ctypes.data) if tickets else None, C.byref(ni)), "raft_engine_append_noops")
-        info = {k: int(getattr(ni, k)) for k in abi.NOOP_INFO_FIELDS}
+        info = abi.info_dict(ni)
         return (info, t, c) if tickets else info
 
     def append_noops_dev(self, ticket_ptr: int, cmd_ptr: int, g0: int = 0, n: int | None = None,
@@ -1323,43 +1258,22 @@ class RaftEngine:
         and their command ids ([n] uint32) written to DEVICE memory, or both
         pointers 0 for none; returns the info once the kernel finished."""
         g0, n, cmd = self._noop_args(g0, n, cmd, "append_noops_dev")
-        if ticket_ptr % 16:
-            raise ValueError("append_noops_dev: the ticket buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("append_noops_dev", after_stream, ticket=ticket_ptr)
         ni = abi.raft_noop_info()
         self._client_status(self._lib.raft_engine_append_noops_dev(
             self._h, g0, n, cmd, C.c_void_p(ticket_ptr or 0), C.c_void_p(cmd_ptr or 0), C.byref(ni)),
             "raft_engine_append_noops_dev")
-        return {k: int(getattr(ni, k)) for k in abi.NOOP_INFO_FIELDS}
+        return abi.info_dict(ni)
 
     def sm_set_noop(self, cmd: int | None = abi.NOOP_CMD):
         """raft_engine_sm_set_noop: from now on sm_apply counts and hashes an
         entry whose command id is `cmd` like any other and writes no register
         for it; cmd=None switches that off (the default).  The setting is the
         engine's: it may be made before sm_configure and outlives reset."""
-        if cmd is not None and (isinstance(cmd, bool) or not isinstance(cmd, (int, np.integer))
-                                or not 0 <= cmd <= 0xFFFFFFFF):
-            raise ValueError(f"sm_set_noop: cmd must be a u32 command id or None, not {cmd!r}")
-        self._check(self._lib.raft_engine_sm_set_noop(self._h, int(cmd is not None), int(cmd or 0)), "sm_set_noop")
+        cmd = _int("sm_set_noop", "cmd", cmd, 0, 0xFFFFFFFF, allow_none=True, want="a u32 command id")
+        self._check(self._lib.raft_engine_sm_set_noop(self._h, int(cmd is not None), cmd or 0), "sm_set_noop")
 
     # -- the leader watch (raft_engine_poll_leaders*, raft_engine_read_watch / write_watch) -----------------
-    def _watch_args(self, g0, n, max_events, what: str):
-        """The poll's arguments, checked before any library call."""
-        n = self.G - g0 if n is None else n
-        for name, v in (("g0", g0), ("n", n)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"{what}: {name} must be an integer, not {v!r}")
-        if max_events is not None and (not isinstance(max_events, (int, np.integer)) or isinstance(max_events, bool)
-                                       or max_events < 0):
-            raise ValueError(f"{what}: max_events must be None or an integer >= 0, not {max_events!r}")
-        return int(g0), int(n)
-
-    def _poll(self, fn, g0, n, out_ptr, room, what: str) -> dict:
-        wi = abi.raft_watch_info()
-        self._check(fn(self._h, g0, n, C.c_void_p(out_ptr or 0), int(room), C.byref(wi)), what)
-        return {k: int(getattr(wi, k)) for k in abi.WATCH_INFO_FIELDS}
-
     def poll_leaders(self, g0: int = 0, n: int | None = None, max_events: int | None = None, peek: bool = False):
         """raft_engine_poll_leaders: the groups of [g0, g0 + n) whose newest
         leader (role LEADER, the highest currentTerm, the lowest index among
@@ -1371,28 +1285,15 @@ class RaftEngine:
         groups that were returned.  peek=True stores nothing and returns no
         event.  info: delivered, pending, and over the whole range gained,
         lost, moved, reterm, leaderless (include/raft_engine.h raft_watch_info)."""
-        g0, n = self._watch_args(g0, n, max_events, "poll_leaders")
-        fn = self._lib.raft_engine_poll_leaders
-        if peek:
-            return self._poll(fn, g0, n, 0, 0, "poll_leaders"), np.zeros(0, dtype=abi.EVENT_DTYPE)
-        if max_events is None:
-            max_events = self._poll(fn, g0, n, 0, 0, "poll_leaders")["pending"]
-        out = np.zeros(max(1, int(max_events)), dtype=abi.EVENT_DTYPE)   # never a null buffer: that would be a peek
-        info = self._poll(fn, g0, n, out.ctypes.data, int(max_events), "poll_leaders")
-        return info, out[: info["delivered"]]
+        call = _stream_call(self, "raft_engine_poll_leaders", *_span("poll_leaders", self.G, g0, n))
+        return _WATCH.host(self._check, "poll_leaders", call, max_events, peek)
 
     def poll_leaders_dev(self, out_ptr: int, max_events: int, g0: int = 0, n: int | None = None,
                          after_stream: int | None = None) -> dict:
         """poll_leaders into a DEVICE buffer of max_events 24-byte records (8-byte
         aligned); returns the info once the kernels finished."""
-        g0, n = self._watch_args(g0, n, max_events, "poll_leaders_dev")
-        if max_events is None or (max_events > 0 and not out_ptr):
-            raise ValueError("poll_leaders_dev: a device buffer and its max_events are required")
-        if out_ptr % 8:
-            raise ValueError("poll_leaders_dev: the record buffer must be 8-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
-        return self._poll(self._lib.raft_engine_poll_leaders_dev, g0, n, out_ptr, max_events, "poll_leaders_dev")
+        return self._records_dev(_WATCH, "poll_leaders_dev", "raft_engine_poll_leaders_dev",
+                                 _span("poll_leaders_dev", self.G, g0, n), out_ptr, max_events, after_stream)
 
     def read_watch(self, g0: int = 0, n: int | None = None) -> np.ndarray:
         """What the watch last reported for groups [g0, g0 + n): [n, 2] int32
@@ -1420,11 +1321,7 @@ class RaftEngine:
         """A new safety audit of this engine, every ledger in its zero state
         (RaftAudit: observe, report, read, write, reset, close).  Closing the
         engine closes its audits first."""
-        a = RaftAudit(self)
-        if not hasattr(self, "_audits"):
-            self._audits = []
-        self._audits.append(weakref.ref(a))
-        return a
+        return self._adopt(RaftAudit(self))
 
     # -- the liveness monitor (raft_monitor_*) ------------------------------------------------------------
     def monitor(self, leaderless_steps: int = 0, stalled_steps: int = abi.MONITOR_STALLED_STEPS, lag_entries: int = 0,
@@ -1438,12 +1335,8 @@ class RaftEngine:
         newest leader (0: off), CHURNING when its highest term rose by
         churn_terms within a window of churn_steps (0: off).  Closing the engine
         closes its monitors first."""
-        m = RaftMonitor(self, leaderless_steps=leaderless_steps, stalled_steps=stalled_steps, lag_entries=lag_entries,
-                        churn_terms=churn_terms, churn_steps=churn_steps)
-        if not hasattr(self, "_monitors"):
-            self._monitors = []
-        self._monitors.append(weakref.ref(m))
-        return m
+        return self._adopt(RaftMonitor(self, leaderless_steps=leaderless_steps, stalled_steps=stalled_steps,
+                                       lag_entries=lag_entries, churn_terms=churn_terms, churn_steps=churn_steps))
 
     # -- the persistence stream (raft_wal_*) ------------------------------------------------------------
     def wal(self) -> RaftWal:
@@ -1451,22 +1344,15 @@ class RaftEngine:
         poll, poll_dev, peek, cursors, set_cursors, reset, device_bytes, close):
         the first poll hands out every replica's hard state and whole log, the
         later ones what changed.  Closing the engine closes its streams first."""
-        w = RaftWal(self)
-        if not hasattr(self, "_wals"):
-            self._wals = []
-        self._wals.append(weakref.ref(w))
-        return w
+        return self._adopt(RaftWal(self))
 
     # -- the proposal outbox (raft_engine_outbox_*, raft_outbox_submit*) ---------------------------------
     def outbox_configure(self, capacity: int, expire_steps: int = 0):
         """raft_engine_outbox_configure: a queue of `capacity` proposals in HBM;
         a record older than expire_steps steps completes EXPIRED (0: never)."""
-        for name, v in (("capacity", capacity), ("expire_steps", expire_steps)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"outbox_configure: {name} {v!r} must be an integer")
-        if not (1 <= capacity < 2 ** 31 and 0 <= expire_steps < 2 ** 31):
-            raise ValueError("outbox_configure: 1 <= capacity < 2^31 and 0 <= expire_steps < 2^31")
-        self._check(self._lib.raft_engine_outbox_configure(self._h, int(capacity), int(expire_steps)), "outbox_configure")
+        capacity = _int("outbox_configure", "capacity", capacity, 1, 2 ** 31 - 1)
+        expire_steps = _int("outbox_configure", "expire_steps", expire_steps, 0, 2 ** 31 - 1)
+        self._check(self._lib.raft_engine_outbox_configure(self._h, capacity, expire_steps), "outbox_configure")
 
     def outbox_submit(self, groups, cmds, tags):
         """raft_outbox_submit: enqueue proposal cmds[m] (a u32 id) for groups[m]
@@ -1483,15 +1369,13 @@ class RaftEngine:
     def outbox_submit_dev(self, group_ptr: int, cmd_ptr: int, tag_ptr: int, n: int, after_stream: int | None = None):
         """raft_outbox_submit_dev: DEVICE pointers to n int64 groups, uint32
         commands and int64 tags."""
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("outbox_submit_dev", after_stream)
         self._check(self._lib.raft_outbox_submit_dev(self._h, group_ptr, cmd_ptr, tag_ptr, int(n)),
                     "raft_outbox_submit_dev")
 
-    def _outbox_info(self, info) -> dict:
-        d = {k: int(getattr(info, k)) for k in abi.OUTBOX_INFO_FIELDS}
-        d["age_hist"] = [int(x) for x in info.age_hist]
-        return d
+    @staticmethod
+    def _outbox_info(info) -> dict:
+        return {**abi.info_dict(info), "age_hist": [int(x) for x in info.age_hist]}
 
     def outbox_len(self) -> int:
         """Records in the outbox now (raft_engine_outbox_read's peek)."""
@@ -1508,24 +1392,18 @@ class RaftEngine:
         records): info has abi.OUTBOX_INFO_FIELDS and age_hist (32 buckets).
         RAFT_EWINDOW (a record UNKNOWN below a log_window, or a retried add
         below one) is not raised: ``last_status`` carries the code."""
-        if max_done is None:
-            max_done = self.outbox_len()
-        if isinstance(max_done, bool) or not isinstance(max_done, (int, np.integer)) or max_done < 0:
-            raise ValueError(f"outbox_pump: max_done {max_done!r} must be an integer >= 0")
-        out = np.zeros(int(max_done), dtype=abi.OUTBOX_DONE_DTYPE)
+        max_done = _int("outbox_pump", "max_done", self.outbox_len() if max_done is None else max_done, 0)
+        out = np.zeros(max_done, dtype=abi.OUTBOX_DONE_DTYPE)
         n, info = C.c_int64(), abi.raft_outbox_info()
         self._client_status(self._lib.raft_engine_outbox_pump(self._h, C.c_void_p(out.ctypes.data) if max_done else None,
-                                                              int(max_done), C.byref(n), C.byref(info)),
+                                                              max_done, C.byref(n), C.byref(info)),
                             "raft_engine_outbox_pump")
         return self._outbox_info(info), out[: int(n.value)]
 
     def outbox_pump_dev(self, done_ptr: int, max_done: int, after_stream: int | None = None):
         """outbox_pump into a DEVICE buffer of max_done 32-byte records (16-byte
         aligned); returns (info, records written)."""
-        if done_ptr % 16:
-            raise ValueError("outbox_pump_dev: the record buffer must be 16-byte aligned")
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("outbox_pump_dev", after_stream, record=done_ptr)
         n, info = C.c_int64(), abi.raft_outbox_info()
         self._client_status(self._lib.raft_engine_outbox_pump_dev(self._h, C.c_void_p(done_ptr), int(max_done),
                                                                   C.byref(n), C.byref(info)),
@@ -1651,22 +1529,19 @@ class RaftEngine:
         """raft_vote_batch_dev: DEVICE pointers to n int64 groups, int32
         replicas, raft_vote_req and raft_vote_resp (e.g. torch tensors'
         data_ptr() on this engine's GPU)."""
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("vote_batch_dev", after_stream)
         self._check(self._lib.raft_vote_batch_dev(self._h, group_ptr, dst_ptr, req_ptr, resp_ptr, int(n)),
                     "raft_vote_batch_dev")
 
     def append_batch_dev(self, group_ptr: int, dst_ptr: int, req_ptr: int, resp_ptr: int, n: int,
                          after_stream: int | None = None):
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("append_batch_dev", after_stream)
         self._check(self._lib.raft_append_batch_dev(self._h, group_ptr, dst_ptr, req_ptr, resp_ptr, int(n)),
                     "raft_append_batch_dev")
 
     def append_command_batch_dev(self, group_ptr: int, replica_ptr: int, cmd_ptr: int, n: int,
                                  after_stream: int | None = None):
-        if after_stream is not None:
-            self.wait_stream(after_stream)
+        self._dev("append_command_batch_dev", after_stream)
         self._check(self._lib.raft_append_command_batch_dev(self._h, group_ptr, replica_ptr, cmd_ptr, int(n)),
                     "raft_append_command_batch_dev")
 

@@ -40,6 +40,84 @@ def test_library_exports_every_declared_symbol(lib):
     assert not missing, missing
 
 
+C_TYPES = {"int16_t": C.c_int16, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+           "uint64_t": C.c_uint64}
+# records of the header that abi has as a numpy dtype only
+DTYPE_ONLY = {"raft_outbox_entry": "OUTBOX_ENTRY_DTYPE", "raft_outbox_done": "OUTBOX_DONE_DTYPE"}
+
+
+def header_structs() -> dict:
+    """name -> [(field, ctype)] of every `typedef struct NAME { ... } NAME;` of
+    include/raft_engine.h (`int64_t a, b[3];` declares two fields)."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "raft_engine.h")).read(), flags=re.S)
+    out = {}
+    for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \1;", src, re.S):
+        decls = re.findall(r"(\w+)\s+([^;]+);", body)
+        assert len(decls) == body.count(";") and all(t in C_TYPES for t, _ in decls), (name, decls)
+        out[name] = []
+        for ctype, names in decls:
+            for k in names.split(","):
+                k, _, count = k.strip().partition("[")
+                out[name].append((k, C_TYPES[ctype] * int(count[:-1]) if count else C_TYPES[ctype]))
+    return out
+
+
+def abi_structs() -> dict:
+    return {k: v for k, v in vars(abi).items()
+            if not k.startswith("_") and isinstance(v, type) and issubclass(v, C.Structure)}
+
+
+def test_every_record_is_in_the_header_and_in_abi():
+    assert set(header_structs()) == set(abi_structs()) | set(DTYPE_ONLY)
+    assert len(abi_structs()) >= 40
+
+
+@pytest.mark.parametrize("name", sorted(header_structs()))
+def test_record_layout_equals_the_header(name):
+    """Every record of the C-ABI: the ctypes.Structure has the header's fields,
+    in its order and of its types; its numpy dtype has the struct's size and
+    offsets; the scalar fields are all but the reserved ones and the arrays."""
+    import numpy as np
+    want = header_structs()[name]
+    names = [k for k, _ in want]
+    if name in DTYPE_ONLY:
+        dtype = getattr(abi, DTYPE_ONLY[name])
+        struct = type(name, (C.Structure,), {"_fields_": want})          # the header's own layout
+    else:
+        struct = abi_structs()[name]
+        dtype = struct.dtype
+        assert [(k, t._type_, getattr(t, "_length_", None)) for k, t in struct._fields_] == \
+               [(k, t._type_, getattr(t, "_length_", None)) for k, t in want]
+        assert struct.scalars == tuple(k for k, t in want if not hasattr(t, "_length_") and not k.startswith("reserved"))
+        assert list(dtype.names) == names
+        if not any(v is dtype for v in vars(abi).values()):
+            return                                   # never handed out as an array (raft_params has tail padding)
+    assert list(dtype.names) == names
+    assert C.sizeof(struct) == dtype.itemsize
+    assert [dtype.fields[k][1] for k in names] == [getattr(struct, k).offset for k in names]
+    assert [dtype.fields[k][0].itemsize for k in names] == [getattr(struct, k).size for k in names]
+
+
+def test_every_public_dtype_and_field_tuple_comes_from_a_record():
+    """No dtype or *_FIELDS tuple of abi is stated a second time: each is a
+    record's own (or one of the two outbox records checked above)."""
+    import numpy as np
+    structs = abi_structs().values()
+    for k, v in vars(abi).items():
+        if isinstance(v, np.dtype):
+            assert k in DTYPE_ONLY.values() or any(v is s.dtype for s in structs), k
+        elif k.endswith("_FIELDS") and isinstance(v, tuple):
+            assert any(v is s.scalars for s in structs), k
+
+
+def test_signature_table_is_what_the_library_binds(lib):
+    """EXPORTED_SYMBOLS is the signature table, and every entry is bound."""
+    assert abi.EXPORTED_SYMBOLS == list(abi.SIGNATURES)
+    for name, (res, args) in abi.SIGNATURES.items():
+        f = getattr(lib, name)
+        assert f.restype is res and list(f.argtypes) == list(args), name
+
+
 def test_library_is_gfx950(lib):
     data = open(abi.LIB_PATH, "rb").read()
     assert b"amdgcn-amd-amdhsa--gfx950" in data          # the embedded code-object bundle id
