@@ -44,7 +44,9 @@ argument meaning and error behaviour:
 * ``RaftService.persist`` / ``recover``: the engine's persistence stream -- the
   hard state and the log entries that changed since the last call, applied to
   a host-side image of every node's disk (etcd's HardState and Entries in a
-  Ready), and a node given back what it had persisted after it lost it
+  Ready), and a node given back what it had persisted after it lost it;
+  ``recover_on_device`` does that for many nodes in one device call (the
+  engine's WAL replay) and ``standby`` keeps a second engine in step from it
 * ``RaftService.leader`` / ``submit`` / ``status``: what a client of the
   reference's ``/cmd/{command}`` route (RaftServer.kt:87-88) needs -- the group's
   leader, a command routed to it with a ticket, and that ticket's fate
@@ -60,7 +62,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import abi, wire
+from . import abi, replay, wire
 from .engine import RaftEngine, WalImage
 
 
@@ -477,6 +479,56 @@ class RaftService:
         e.write_log(t, c, group)
         e.write_state(st, group)
         return {"term": int(im.term[group, replica]), "vote": int(im.vote[group, replica]), "length": n}
+
+    def recover_on_device(self, nodes) -> dict:
+        """recover for many nodes at once, without a host copy of a group:
+        `nodes` is a sequence of (group, replica) pairs (one named twice counts
+        once); their replay.image_records, in (group, replica) order, are one
+        replay.replay.  Each node gets back the image's currentTerm,
+        votedFor and log and comes up as a restarted node does (FOLLOWER,
+        commitIndex 0, a fresh election timeout); the other nodes do not
+        change.  Of a ring image longer than the log_window only the newest
+        log_window entries are sent, and no TRUNCATE: the node's lastIndex must
+        then be at or below the first of them, as after restart(amnesia=True).
+        Returns the replay's info."""
+        if getattr(self, "wal_image", None) is None:
+            raise ValueError("recover_on_device: nothing was persisted (persist() first)")
+        e, im = self.engine, self.wal_image
+        pairs = sorted({(int(g), int(r)) for g, r in nodes})
+        if any(not (0 <= g < e.G and 0 <= r < e.R) for g, r in pairs):
+            raise IndexError("recover_on_device: a node outside the engine")
+        W = int(e.p.log_window)
+        parts = []
+        for g, r in pairs:
+            rec = replay.image_records(im, g, r)
+            if W and len(rec) - 2 > W:
+                rec = np.concatenate([rec[:1], rec[-W:]])
+            parts.append(rec)
+        batch = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.WAL_RECORD_DTYPE)
+        return replay.replay(e, batch)
+
+    def standby(self, other: "RaftService", max_records: Optional[int] = None) -> dict:
+        """Bring `other`'s engine (same R, mode, log_cap and log_window, never
+        stepped) up to this engine's persistent state: RaftWal.poll of this
+        service's stream (``wal``, made at the first call) and replay.replay
+        with keep_volatile into other.engine, until nothing is pending.  ``wal``
+        is the stream persist() uses: a service feeds its image or a standby,
+        not both.  Returns the totals (polls, applied, hardstates, truncates,
+        entries, lost)."""
+        if getattr(self, "wal", None) is None:
+            self.wal = self.engine.wal()
+        tot = {k: 0 for k in ("polls", "applied", "hardstates", "truncates", "entries", "lost")}
+        while True:
+            rec, info = self.wal.poll(max_records=max_records)
+            done = replay.replay(other.engine, rec, keep_volatile=True)
+            tot["polls"] += 1
+            tot["lost"] += info["lost"]
+            for k in ("applied", "hardstates", "truncates", "entries"):
+                tot[k] += done[k]
+            if not info["pending"]:
+                return tot
+            if not info["delivered"]:
+                raise ValueError("standby: max_records leaves no room for a record")
 
     # -- leadership transfer (Raft thesis §3.10; the reference's leader only loses leadership by timeout) ---
     def transfer_leadership(self, group: int, to: Optional[int] = None) -> str:
