@@ -623,3 +623,20 @@ def load_library(path: str | None = None):
         f.argtypes = args
     _lib = lib if path is None else _lib
     return lib
+
+
+def bind_extension(lib, signatures: dict, mark: str):
+    """What the extension modules (replay.py, debug.py) share: `lib` (None: the
+    engine library) with restype and argtypes of `signatures` bound, once per
+    library (`mark` is the attribute that remembers it).  There is no fallback:
+    a library without one of the entry points raises."""
+    lib = lib or load_library()
+    if getattr(lib, mark, False):
+        return lib
+    for name, (res, args) in signatures.items():
+        if not hasattr(lib, name):
+            raise RuntimeError(f"{name} is not in this engine build: rebuild it (`python raft-kotlin_amd/build.py`)")
+        f = getattr(lib, name)
+        f.restype, f.argtypes = res, args
+    setattr(lib, mark, True)
+    return lib

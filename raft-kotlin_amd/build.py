@@ -38,12 +38,14 @@ SRCS = [SRC, os.path.join(CSRC, "raft_batch.hip"),                   # the handl
         os.path.join(CSRC, "raft_wal.hip"),                          # the persistence stream (hard state, log deltas)
         os.path.join(CSRC, "raft_nemesis.hip"),                      # scripted network faults (isolate, heal, list)
         os.path.join(CSRC, "raft_replay.hip"),                       # WAL replay (replicas rebuilt from the stream)
+        os.path.join(CSRC, "raft_debug.hip"),                        # the log-tail cache read back (a test window)
         os.path.join(CSRC, "raft_wire.cpp"),                         # the wire codec is host code
         os.path.join(CSRC, "raft_host.cpp"),                         # page-locked batch memory
         os.path.join(CSRC, "raft_comm.cpp")]                         # the RCCL counter all-reduce (dlopen)
 HDRS = [os.path.join(CSRC, h) for h in ("raft_step.h", "philox.h", "raft_engine_impl.h", "raft_ticket.h",
                                            "raft_stream.h")] + [
-    os.path.join(ROOT, "include", h) for h in ("raft_engine.h", "raft_wire.h", os.path.join("ext", "raft_replay.h"))]
+    os.path.join(ROOT, "include", h) for h in ("raft_engine.h", "raft_wire.h", os.path.join("ext", "raft_replay.h"),
+                                               os.path.join("ext", "raft_debug.h"))]
 # the step kernel's sources (bench.py's kernel_source_id, the key of its
 # rocprofv3 rows): not raft_batch.hip, which holds no step-kernel code
 KERNEL_SOURCES = ("raft_step.h", "raft_engine.hip", "philox.h", "raft_engine_impl.h")

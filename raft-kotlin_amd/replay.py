@@ -41,16 +41,7 @@ EXPORTED_SYMBOLS = list(SIGNATURES)
 def bind(lib=None):
     """The engine library with the entry points of this extension bound
     (restype and argtypes of SIGNATURES).  Raises if the library lacks one."""
-    lib = lib or abi.load_library()
-    if getattr(lib, "_raft_replay_bound", False):
-        return lib
-    for name, (res, args) in SIGNATURES.items():
-        if not hasattr(lib, name):
-            raise RuntimeError(f"{name} is not in this engine build: rebuild it (`python raft-kotlin_amd/build.py`)")
-        f = getattr(lib, name)
-        f.restype, f.argtypes = res, args
-    lib._raft_replay_bound = True
-    return lib
+    return abi.bind_extension(lib, SIGNATURES, "_raft_replay_bound")
 
 
 def _call(engine: RaftEngine, name: str, ptr: int, n: int, keep_volatile: bool) -> dict:

@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 
 import oracle as O
-from helpers import (abi, assert_same_logs, assert_same_state, blank_groups, fld, log_matching_flags, set_fld,
-                     set_session, session)
+from helpers import (abi, assert_same_logs, assert_same_state, blank_groups, fld, handler_messages,
+                     log_matching_flags, random_ring_states, random_states, set_fld, set_session, session)
 
 pytestmark = pytest.mark.gpu
 
@@ -706,64 +706,6 @@ def test_window_misses_are_counted():
 
 
 # ---- the service boundary: single handlers vs the oracle -------------------------
-
-def random_states(rng, n, R, cap):
-    w = blank_groups(n, R)
-    logs_t = rng.integers(0, 4, size=(n, R, cap)).astype(np.int32)
-    logs_t.sort(axis=2)
-    logs_c = rng.integers(0, 1 << 32, size=(n, R, cap), dtype=np.uint64).astype(np.uint32)
-    for r in range(R):
-        phys = rng.integers(0, cap + 1, size=n)
-        last = (phys * rng.random(n)).astype(np.int32)
-        set_fld(w, R, r, "phys", phys)
-        set_fld(w, R, r, "last", last)
-        set_fld(w, R, r, "term", rng.integers(0, 5, size=n))
-        set_fld(w, R, r, "voted", rng.integers(-1, R + 1, size=n))
-        set_fld(w, R, r, "role", rng.integers(0, 3, size=n))
-        set_fld(w, R, r, "commit", rng.integers(0, 6, size=n))
-        set_fld(w, R, r, "flags", rng.choice([0, abi.FL_ARMED, abi.FL_ELECTING, abi.FL_ELECTING | abi.FL_PENDING_RST],
-                                             size=n))
-    return w, logs_t, logs_c
-
-
-def random_ring_states(rng, n, R, cap, window):
-    """States for a log_window ring whose handler batches stay inside the
-    window: physLen up to cap (the ring wraps), lastIndex at most window / 2
-    below it, so every Log.get / overwrite the requests below make reads a
-    retained slot."""
-    w, logs_t, logs_c = random_states(rng, n, R, cap)
-    for r in range(R):
-        phys = rng.integers(0, cap + 1, size=n)
-        last = np.maximum(0, phys - rng.integers(0, window // 2, size=n))
-        set_fld(w, R, r, "phys", phys)
-        set_fld(w, R, r, "last", last)
-    return w, logs_t, logs_c
-
-
-def handler_messages(rng, n, G, R, cap, w=None, window=0):
-    """n random (group, dst) and vote / append / command requests; on a ring
-    (window > 0) the indices they read stay within window / 4 of the target's
-    lastIndex (see random_ring_states)."""
-    grp = rng.integers(0, G, size=n)
-    dst = rng.integers(0, R, size=n).astype(np.int32)
-    if window:
-        last = np.array([fld(w[g], R, d, "last") for g, d in zip(grp, dst)])
-        phys = np.array([fld(w[g], R, d, "phys") for g, d in zip(grp, dst)])
-        li = np.maximum(0, last - rng.integers(0, 4, n))
-        prev = last - 1 - rng.integers(0, window // 4, n)
-        prev = np.where(prev < phys - window + window // 4, np.maximum(last - 1, -1), prev)
-        prev = np.where((prev < 0) & (phys > window // 2), last - 1, np.maximum(prev, -1))
-    else:
-        li = rng.integers(0, cap + 1, n)
-        prev = rng.integers(-1, cap, n)
-    vq = np.stack([rng.integers(0, 6, n), rng.integers(1, R + 1, n), li, rng.integers(0, 4, n)],
-                  axis=1).astype(np.int32)
-    aq = np.stack([rng.integers(0, 6, n), rng.integers(1, R + 1, n), prev,
-                   rng.integers(-1, 4, n), rng.integers(0, 2, n), rng.integers(0, 6, n),
-                   rng.integers(0, 1 << 32, n, dtype=np.uint64), rng.integers(0, 8, n)], axis=1).astype(np.int64)
-    cmd = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    return grp, dst, vq, aq, cmd
-
 
 HANDLER_CASES = [
     # (R, mode, G, n, log_window): long per-replica runs (G = 64 groups: ~15-50
