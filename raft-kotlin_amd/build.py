@@ -43,7 +43,7 @@ SRCS = [SRC, os.path.join(CSRC, "raft_batch.hip"),                   # the handl
         os.path.join(CSRC, "raft_host.cpp"),                         # page-locked batch memory
         os.path.join(CSRC, "raft_comm.cpp")]                         # the RCCL counter all-reduce (dlopen)
 HDRS = [os.path.join(CSRC, h) for h in ("raft_step.h", "philox.h", "raft_engine_impl.h", "raft_ticket.h",
-                                           "raft_stream.h")] + [
+                                           "raft_stream.h", "raft_ledger.h")] + [
     os.path.join(ROOT, "include", h) for h in ("raft_engine.h", "raft_wire.h", os.path.join("ext", "raft_replay.h"),
                                                os.path.join("ext", "raft_debug.h"))]
 # the step kernel's sources (bench.py's kernel_source_id, the key of its

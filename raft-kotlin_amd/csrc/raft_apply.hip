@@ -25,7 +25,7 @@
 #include <algorithm>
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) void apply_expand_kernel(DevParams p, int32_
 
 template <int R> struct CountL {
     static void run(raft_engine* e, const Sel& s, int peek, uint32_t* cnt, unsigned long long* hdr) {
-        const unsigned grid = (unsigned)((s.N + 1 + BLOCK - 1) / BLOCK);
+        const unsigned grid = grid_of(s.N + 1);
         apply_count_kernel<R><<<grid, BLOCK, 0, e->stream>>>(e->dp, e->applied, s, peek, cnt, hdr);
     }
 };
@@ -226,28 +226,19 @@ int raft_engine_drain_committed_dev(raft_engine* e, int64_t g0, int64_t n, int32
     return drain(e, g0, n, replica, out_dev, max_entries, info, false);
 }
 
+// replicas are indexed g * R + r: a range of groups is one contiguous run of lastApplied
 int raft_engine_read_applied(raft_engine* e, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    HIP_TRY(hipSetDevice(e->device));
-    // replicas are indexed g * R + r: the range is one contiguous run
-    HIP_TRY(hipMemcpyAsync(out, e->applied + g0 * e->p.R, (size_t)n * e->p.R * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_groups(e, g0, n), n, out,
+                      [&] { return rows_out(e, e->applied + g0 * e->p.R, (size_t)n * e->p.R * 4, out); });
 }
 
 int raft_engine_write_applied(raft_engine* e, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    for (int64_t k = 0; k < n * e->p.R; ++k)         // a drain reads log slots [lastApplied, hi): keep it inside the row
-        if (in[k] < 0 || in[k] > e->p.log_cap)
-            return raft_internal_fail(RAFT_EINVAL, "lastApplied must be in 0..log_cap");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(e->applied + g0 * e->p.R, in, (size_t)n * e->p.R * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_groups(e, g0, n), n, in, [&]() -> int {
+        for (int64_t k = 0; k < n * e->p.R; ++k)     // a drain reads log slots [lastApplied, hi): keep it inside the row
+            if (in[k] < 0 || in[k] > e->p.log_cap)
+                return raft_internal_fail(RAFT_EINVAL, "lastApplied must be in 0..log_cap");
+        return rows_in(e, e->applied + g0 * e->p.R, in, (size_t)n * e->p.R * 4);
+    });
 }
 
 // Not in the header (scripts/drain_probe.py): while enabled, a drain records an

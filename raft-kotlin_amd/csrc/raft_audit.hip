@@ -31,14 +31,11 @@
 #include <string>
 #include <vector>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
-struct raft_audit {
-    raft_engine* e;
-    char* mem;                  // one allocation: hdr [G] of 32 bytes, then pairs [G * R] of 8 bytes
-    size_t bytes;
+struct raft_audit : raft_ledger {   // mem: hdr [G] of 32 bytes, then pairs [G * R] of 8 bytes, 256-byte aligned each
     int4* hdr;
     int2* pairs;
 };
@@ -47,7 +44,6 @@ namespace {
 
 static_assert(sizeof(raft_audit_event) == 16 && sizeof(raft_audit_info) == 64 && sizeof(raft_audit_report_info) == 64,
               "record layouts of the C-ABI");
-static_assert(RAFT_MAX_R == 8, "eight lanes per group");
 
 constexpr uint32_t AUDIT_ALL = RAFT_AUDIT_TERM_REGRESSED | RAFT_AUDIT_VOTE_CHANGED | RAFT_AUDIT_TWO_LEADERS |
                                RAFT_AUDIT_COMMIT_CHANGED | RAFT_AUDIT_LEADER_INCOMPLETE;
@@ -55,28 +51,6 @@ constexpr uint32_t AUDIT_ALL = RAFT_AUDIT_TERM_REGRESSED | RAFT_AUDIT_VOTE_CHANG
 // the counts of an observe, striped as a restart's totals, at the head of aux; a report uses word 0 alone
 enum { AW_NEWLY = 0, AW_FLAGGED, AW_TERM, AW_VOTE, AW_TWO, AW_COMMIT, AW_LEADER, AW_UNKNOWN, AW_WORDS };
 using Counts = DevWords<unsigned long long, HDR_STRIPES, HDR_LINE, AW_WORDS, true>;
-
-// over the eight lanes of a group (every lane of the wave takes part)
-__device__ __forceinline__ int32_t group_max(int32_t v) {
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ long long group_max64(long long v) {
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t group_or(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v |= __shfl_xor(v, d, 64);
-    return v;
-}
-// the group's byte of a ballot: bit r is its lane r
-__device__ __forceinline__ uint32_t group_bits(unsigned long long ballot) {
-    return (uint32_t)(ballot >> (threadIdx.x & 56)) & 0xFFu;
-}
-__device__ __forceinline__ bool differ(int4 a, int4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; }
 
 __global__ __launch_bounds__(BLOCK) void audit_fill_kernel(int4* __restrict__ hdr, int2* __restrict__ pairs, int64_t g0,
                                                            int64_t n, int R) {
@@ -221,36 +195,20 @@ struct AuditSource {
     static int64_t total(const unsigned long long* w) { return (int64_t)w[0]; }
 };
 
-int check_audit(raft_audit* a, int64_t g0, int64_t n) {
-    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
-    return check_groups(a->e, g0, n);
-}
-
 // the zero state of groups [g0, g0 + n), enqueued on the engine stream
 int fill(raft_audit* a, int64_t g0, int64_t n) {
     const int R = a->e->p.R;
-    const unsigned grid = (unsigned)((n * R + BLOCK - 1) / BLOCK);
-    audit_fill_kernel<<<grid, BLOCK, 0, a->e->stream>>>(a->hdr, a->pairs, g0, n, R);
+    audit_fill_kernel<<<grid_of(n * R), BLOCK, 0, a->e->stream>>>(a->hdr, a->pairs, g0, n, R);
     HIP_TRY(hipGetLastError());
     return RAFT_OK;
 }
 
 int report(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out, int64_t max_events,
            raft_audit_report_info* info, bool out_on_host) {
-    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
-    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    *info = raft_audit_report_info{};
-    raft_engine* e = a->e;
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (int rc = check_records(out, max_events, out_on_host, 16, "max_events")) return rc;
-    if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    StreamTotals<AuditSource> c{};
-    const int rc = stream_records(e, AuditSource{a->hdr}, g0, n, out, max_events, out_on_host, c, &info->delivered);
-    info->flagged = AuditSource::total(c.w);
-    info->pending = info->flagged - info->delivered;
-    return rc;
+    return ledger_report<AuditSource>(a, "null audit", g0, n, out, max_events, out_on_host, info, [&](AuditSource& s) {
+        s.hdr = a->hdr;
+        return RAFT_OK;
+    });
 }
 
 }  // namespace
@@ -258,68 +216,33 @@ int report(raft_audit* a, int64_t g0, int64_t n, raft_audit_event* out, int64_t 
 extern "C" {
 
 int raft_audit_create(raft_engine* e, raft_audit** out) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null out");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(e->device));
-    raft_audit* a = new raft_audit{};
-    a->e = e;
+    if (int rc = create_args(e, out)) return rc;
     const size_t hdr_b = al256((size_t)e->p.G * 32), pair_b = al256((size_t)e->dp.GR * 8);
-    if (hipMalloc((void**)&a->mem, hdr_b + pair_b) != hipSuccess) {
-        delete a;
-        return raft_internal_fail(RAFT_ENOMEM, "the audit's ledger: hipMalloc failed");
-    }
-    a->bytes = hdr_b + pair_b;
-    a->hdr = (int4*)a->mem;
-    a->pairs = (int2*)(a->mem + hdr_b);
-    if (int rc = raft_audit_reset(a)) {
-        (void)hipFree(a->mem);
-        delete a;
-        return rc;
-    }
-    *out = a;
-    return RAFT_OK;
+    return ledger_create(e, out, hdr_b + pair_b, "the audit's ledger", [&](raft_audit* a) {
+        a->hdr = (int4*)a->mem;
+        a->pairs = (int2*)(a->mem + hdr_b);
+        return raft_audit_reset(a);
+    });
 }
 
-int raft_audit_destroy(raft_audit* a) {
-    if (!a) return RAFT_OK;
-    if (a->e) {
-        (void)hipSetDevice(a->e->device);
-        (void)hipStreamSynchronize(a->e->stream);
-    }
-    (void)hipFree(a->mem);
-    delete a;
-    return RAFT_OK;
-}
+int raft_audit_destroy(raft_audit* a) { return ledger_destroy(a); }
 
 int raft_audit_reset(raft_audit* a) {
-    if (int rc = check_audit(a, 0, 0)) return rc;
-    raft_engine* e = a->e;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    if (int rc = fill(a, 0, e->p.G)) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return ledger_reset(a, "null audit", [&](raft_engine* e) {
+        e->fork_needed = true;
+        return fill(a, 0, e->p.G);
+    });
 }
 
-int64_t raft_audit_device_bytes(raft_audit* a) { return a ? (int64_t)a->bytes : 0; }
+int64_t raft_audit_device_bytes(raft_audit* a) { return ledger_bytes(a); }
 
 int raft_audit_observe(raft_audit* a, int64_t g0, int64_t n, raft_audit_info* info) {
-    if (!a || !a->e) return raft_internal_fail(RAFT_EINVAL, "null audit");
-    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    *info = raft_audit_info{};
-    raft_engine* e = a->e;
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;                           // later step launches wait for these reads of the state
-    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Counts::BYTES)) return rc;
-    Counts c;
-    if (int rc = c.zero(e, e->aux)) return rc;
-    const unsigned grid = (unsigned)((n * 8 + BLOCK - 1) / BLOCK);
-    audit_observe_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, a->hdr, a->pairs, g0, n, (int32_t)(uint32_t)e->t, c.dev);
-    HIP_TRY(hipGetLastError());
-    if (int rc = c.fetch(e)) return rc;
+    Counts c{};
+    if (int rc = ledger_observe(a, "null audit", g0, n, info, c, [&](unsigned grid, unsigned long long* cnt) {
+            audit_observe_kernel<<<grid, BLOCK, 0, a->e->stream>>>(a->e->dp, a->hdr, a->pairs, g0, n,
+                                                                   (int32_t)(uint32_t)a->e->t, cnt);
+        }))
+        return rc;
     info->newly_flagged = (int64_t)c.w[AW_NEWLY];
     info->flagged = (int64_t)c.w[AW_FLAGGED];
     info->term_regressed = (int64_t)c.w[AW_TERM];
@@ -341,48 +264,40 @@ int raft_audit_report_dev(raft_audit* a, int64_t g0, int64_t n, raft_audit_event
     return report(a, g0, n, out_dev, max_events, info, false);
 }
 
+// the exported row of a group is its two header quads, then its R pairs: two regions on the device
 int raft_audit_read(raft_audit* a, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_audit(a, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = a->e;
-    const int R = e->p.R, W = 8 + 2 * R;
-    std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(h.data(), a->hdr + 2 * g0, h.size() * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(pr.data(), a->pairs + g0 * R, pr.size() * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int64_t k = 0; k < n; ++k) {
-        std::memcpy(out + k * W, h.data() + k * 8, 32);
-        std::memcpy(out + k * W + 8, pr.data() + k * R * 2, (size_t)R * 8);
-    }
-    return RAFT_OK;
+    return table_call(check_ledger(a, g0, n, "null audit"), n, out, [&]() -> int {
+        const int R = a->e->p.R, W = 8 + 2 * R;
+        std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
+        if (int rc = rows_out(a->e, {{a->hdr + 2 * g0, h.data(), h.size() * 4}, {a->pairs + g0 * R, pr.data(), pr.size() * 4}}))
+            return rc;
+        for (int64_t k = 0; k < n; ++k) {
+            std::memcpy(out + k * W, h.data() + k * 8, 32);
+            std::memcpy(out + k * W + 8, pr.data() + k * R * 2, (size_t)R * 8);
+        }
+        return RAFT_OK;
+    });
 }
 
 int raft_audit_write(raft_audit* a, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_audit(a, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = a->e;
-    const int R = e->p.R, W = 8 + 2 * R;
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t* w = in + k * W;
-        if ((uint32_t)w[0] & ~AUDIT_ALL) return raft_internal_fail(RAFT_EINVAL, "a ledger's flags hold unknown bits");
-        if (w[3] < -1 || w[3] >= R) return raft_internal_fail(RAFT_EINVAL, "a ledger's lead_replica must be in -1..R-1");
-        if (w[4] < 0 || w[4] > e->p.log_cap)
-            return raft_internal_fail(RAFT_EINVAL, "a ledger's anchor_count must be in 0..log_cap");
-    }
-    std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
-    for (int64_t k = 0; k < n; ++k) {
-        std::memcpy(h.data() + k * 8, in + k * W, 32);
-        std::memcpy(pr.data() + k * R * 2, in + k * W + 8, (size_t)R * 8);
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    HIP_TRY(hipMemcpyAsync(a->hdr + 2 * g0, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(a->pairs + g0 * R, pr.data(), pr.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_ledger(a, g0, n, "null audit"), n, in, [&]() -> int {
+        raft_engine* e = a->e;
+        const int R = e->p.R, W = 8 + 2 * R;
+        for (int64_t k = 0; k < n; ++k) {
+            const int32_t* w = in + k * W;
+            if ((uint32_t)w[0] & ~AUDIT_ALL) return raft_internal_fail(RAFT_EINVAL, "a ledger's flags hold unknown bits");
+            if (w[3] < -1 || w[3] >= R) return raft_internal_fail(RAFT_EINVAL, "a ledger's lead_replica must be in -1..R-1");
+            if (w[4] < 0 || w[4] > e->p.log_cap)
+                return raft_internal_fail(RAFT_EINVAL, "a ledger's anchor_count must be in 0..log_cap");
+        }
+        std::vector<int32_t> h((size_t)n * 8), pr((size_t)n * R * 2);
+        for (int64_t k = 0; k < n; ++k) {
+            std::memcpy(h.data() + k * 8, in + k * W, 32);
+            std::memcpy(pr.data() + k * R * 2, in + k * W + 8, (size_t)R * 8);
+        }
+        e->fork_needed = true;
+        return rows_in(e, {{a->hdr + 2 * g0, h.data(), h.size() * 4}, {a->pairs + g0 * R, pr.data(), pr.size() * 4}});
+    });
 }
 
 }  // extern "C"

@@ -35,15 +35,12 @@
 #include <string>
 #include <vector>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
-struct raft_monitor {
-    raft_engine* e;
+struct raft_monitor : raft_ledger {   // mem: the ledger [G] of 64 bytes, then the availability totals, 256-byte aligned each
     raft_monitor_config cfg;
-    char* mem;                  // one allocation: the ledger [G] of 64 bytes, then the availability totals
-    size_t bytes;
     int4* led;
     unsigned long long* avail;  // raft_monitor_availability as it lies: hist[32], outages, down_steps, reserved[2]
 };
@@ -53,7 +50,6 @@ namespace {
 static_assert(sizeof(raft_monitor_config) == 32 && sizeof(raft_monitor_info) == 96 && sizeof(raft_monitor_event) == 32 &&
                   sizeof(raft_monitor_report_info) == 64 && sizeof(raft_monitor_availability) == 288,
               "record layouts of the C-ABI");
-static_assert(RAFT_MAX_R == 8, "eight lanes per group");
 
 constexpr int AVAIL_WORDS = sizeof(raft_monitor_availability) / 8, AV_OUTAGES = 32, AV_DOWN_STEPS = 33;
 constexpr int LEDGER_WORDS = 16;
@@ -64,22 +60,6 @@ enum { MW_FLAGGED = 0, MW_NEWLY, MW_CLEARED, MW_LEADERLESS, MW_STALLED, MW_LAGGI
 constexpr int MON_LINE = 16;
 using Counts = DevWords<unsigned long long, HDR_STRIPES, MON_LINE, MW_WORDS, true>;
 
-// over the eight lanes of a group (every lane of the wave takes part)
-__device__ __forceinline__ int32_t group_max(int32_t v) {
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ long long group_max64(long long v) {
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-// the group's byte of a ballot: bit r is its lane r
-__device__ __forceinline__ uint32_t group_bits(unsigned long long ballot) {
-    return (uint32_t)(ballot >> (threadIdx.x & 56)) & 0xFFu;
-}
-__device__ __forceinline__ bool differ(int4 a, int4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; }
 // age(x) = max(0, (int32)(s - x)), the subtraction taken mod 2^32
 __device__ __forceinline__ int32_t age(int32_t s, int32_t x) { return max(0, (int32_t)((uint32_t)s - (uint32_t)x)); }
 __device__ __forceinline__ int32_t sat_add(int32_t a, int32_t b) {      // a, b >= 0
@@ -256,11 +236,6 @@ struct MonitorSource {
     static int64_t total(const unsigned long long* w) { return (int64_t)w[0]; }
 };
 
-int check_monitor(raft_monitor* m, int64_t g0, int64_t n) {
-    if (!m || !m->e) return raft_internal_fail(RAFT_EINVAL, "null monitor");
-    return check_groups(m->e, g0, n);
-}
-
 int check_config(const raft_monitor_config* c) {
     if (!c) return raft_internal_fail(RAFT_EINVAL, "null config");
     if (c->leaderless_steps < 0 || c->stalled_steps < 0 || c->lag_entries < 0 || c->churn_terms < 0 || c->churn_steps < 0)
@@ -274,24 +249,13 @@ int check_config(const raft_monitor_config* c) {
 
 int report(raft_monitor* m, int64_t g0, int64_t n, int32_t which, int32_t kinds, raft_monitor_event* out,
            int64_t max_events, raft_monitor_report_info* info, bool out_on_host) {
-    if (!m || !m->e) return raft_internal_fail(RAFT_EINVAL, "null monitor");
-    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    *info = raft_monitor_report_info{};
-    raft_engine* e = m->e;
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (which != RAFT_MONITOR_NOW && which != RAFT_MONITOR_EVER)
-        return raft_internal_fail(RAFT_EINVAL, "which must be RAFT_MONITOR_NOW or RAFT_MONITOR_EVER");
-    if ((uint32_t)kinds & ~(uint32_t)RAFT_MONITOR_ALL) return raft_internal_fail(RAFT_EINVAL, "kinds holds unknown bits");
-    if (int rc = check_records(out, max_events, out_on_host, 16, "max_events")) return rc;
-    if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    StreamTotals<MonitorSource> c{};
-    const int rc = stream_records(e, MonitorSource{m->led, which, kinds}, g0, n, out, max_events, out_on_host, c,
-                                  &info->delivered);
-    info->flagged = MonitorSource::total(c.w);
-    info->pending = info->flagged - info->delivered;
-    return rc;
+    return ledger_report<MonitorSource>(m, "null monitor", g0, n, out, max_events, out_on_host, info, [&](MonitorSource& s) {
+        if (which != RAFT_MONITOR_NOW && which != RAFT_MONITOR_EVER)
+            return raft_internal_fail(RAFT_EINVAL, "which must be RAFT_MONITOR_NOW or RAFT_MONITOR_EVER");
+        if ((uint32_t)kinds & ~(uint32_t)RAFT_MONITOR_ALL) return raft_internal_fail(RAFT_EINVAL, "kinds holds unknown bits");
+        s = MonitorSource{m->led, which, kinds};
+        return (int)RAFT_OK;
+    });
 }
 
 }  // namespace
@@ -299,74 +263,38 @@ int report(raft_monitor* m, int64_t g0, int64_t n, int32_t which, int32_t kinds,
 extern "C" {
 
 int raft_monitor_create(raft_engine* e, const raft_monitor_config* cfg, raft_monitor** out) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null out");
-    *out = nullptr;
+    if (int rc = create_args(e, out)) return rc;
     if (int rc = check_config(cfg)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    raft_monitor* m = new raft_monitor{};
-    m->e = e;
-    m->cfg = *cfg;
     const size_t led_b = al256((size_t)e->p.G * 64), av_b = al256(sizeof(raft_monitor_availability));
-    if (hipMalloc((void**)&m->mem, led_b + av_b) != hipSuccess) {
-        delete m;
-        return raft_internal_fail(RAFT_ENOMEM, "the monitor's ledger: hipMalloc failed");
-    }
-    m->bytes = led_b + av_b;
-    m->led = (int4*)m->mem;
-    m->avail = (unsigned long long*)(m->mem + led_b);
-    if (int rc = raft_monitor_reset(m)) {
-        (void)hipFree(m->mem);
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return RAFT_OK;
+    return ledger_create(e, out, led_b + av_b, "the monitor's ledger", [&](raft_monitor* m) {
+        m->cfg = *cfg;
+        m->led = (int4*)m->mem;
+        m->avail = (unsigned long long*)(m->mem + led_b);
+        return raft_monitor_reset(m);
+    });
 }
 
-int raft_monitor_destroy(raft_monitor* m) {
-    if (!m) return RAFT_OK;
-    if (m->e) {
-        (void)hipSetDevice(m->e->device);
-        (void)hipStreamSynchronize(m->e->stream);
-    }
-    (void)hipFree(m->mem);
-    delete m;
-    return RAFT_OK;
-}
+int raft_monitor_destroy(raft_monitor* m) { return ledger_destroy(m); }
 
 int raft_monitor_reset(raft_monitor* m) {
-    if (int rc = check_monitor(m, 0, 0)) return rc;
-    raft_engine* e = m->e;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    const unsigned grid = (unsigned)((e->p.G + BLOCK - 1) / BLOCK);
-    monitor_fill_kernel<<<grid, BLOCK, 0, e->stream>>>(m->led, 0, e->p.G);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(m->avail, 0, sizeof(raft_monitor_availability), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return ledger_reset(m, "null monitor", [&](raft_engine* e) -> int {
+        e->fork_needed = true;
+        monitor_fill_kernel<<<grid_of(e->p.G), BLOCK, 0, e->stream>>>(m->led, 0, e->p.G);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(m->avail, 0, sizeof(raft_monitor_availability), e->stream));
+        return RAFT_OK;
+    });
 }
 
-int64_t raft_monitor_device_bytes(raft_monitor* m) { return m ? (int64_t)m->bytes : 0; }
+int64_t raft_monitor_device_bytes(raft_monitor* m) { return ledger_bytes(m); }
 
 int raft_monitor_observe(raft_monitor* m, int64_t g0, int64_t n, raft_monitor_info* info) {
-    if (!m || !m->e) return raft_internal_fail(RAFT_EINVAL, "null monitor");
-    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    *info = raft_monitor_info{};
-    raft_engine* e = m->e;
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;                           // later step launches wait for these reads of the state
-    if (int rc = raft_internal_grow_dev(e, &e->aux, &e->aux_bytes, Counts::BYTES)) return rc;
-    Counts c;
-    if (int rc = c.zero(e, e->aux)) return rc;
-    const unsigned grid = (unsigned)((n * 8 + BLOCK - 1) / BLOCK);
-    monitor_observe_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, m->cfg, m->led, m->avail, g0, n,
-                                                          (int32_t)(uint32_t)e->t, c.dev);
-    HIP_TRY(hipGetLastError());
-    if (int rc = c.fetch(e)) return rc;
+    Counts c{};
+    if (int rc = ledger_observe(m, "null monitor", g0, n, info, c, [&](unsigned grid, unsigned long long* cnt) {
+            monitor_observe_kernel<<<grid, BLOCK, 0, m->e->stream>>>(m->e->dp, m->cfg, m->led, m->avail, g0, n,
+                                                                     (int32_t)(uint32_t)m->e->t, cnt);
+        }))
+        return rc;
     info->flagged = (int64_t)c.w[MW_FLAGGED];
     info->newly_flagged = (int64_t)c.w[MW_NEWLY];
     info->cleared = (int64_t)c.w[MW_CLEARED];
@@ -390,63 +318,45 @@ int raft_monitor_report_dev(raft_monitor* m, int64_t g0, int64_t n, int32_t whic
     return report(m, g0, n, which, kinds, out_dev, max_events, info, false);
 }
 
+// the availability totals are one row of the handle, not of a group: its own null word, no fork_needed on a set
 int raft_monitor_get_availability(raft_monitor* m, raft_monitor_availability* out) {
-    if (int rc = check_monitor(m, 0, 0)) return rc;
+    if (int rc = check_ledger(m, 0, 0, "null monitor")) return rc;
     if (!out) return raft_internal_fail(RAFT_EINVAL, "null availability");
-    raft_engine* e = m->e;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(out, m->avail, sizeof(*out), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return rows_out(m->e, m->avail, sizeof(*out), out);
 }
 
 int raft_monitor_set_availability(raft_monitor* m, const raft_monitor_availability* in) {
-    if (int rc = check_monitor(m, 0, 0)) return rc;
+    if (int rc = check_ledger(m, 0, 0, "null monitor")) return rc;
     if (!in) return raft_internal_fail(RAFT_EINVAL, "null availability");
     const int64_t* w = (const int64_t*)in;
     for (int i = 0; i < AVAIL_WORDS; ++i)
         if (w[i] < 0) return raft_internal_fail(RAFT_EINVAL, "an availability total must be >= 0");
     if (in->reserved[0] || in->reserved[1]) return raft_internal_fail(RAFT_EINVAL, "the reserved words must be 0");
-    raft_engine* e = m->e;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(m->avail, in, sizeof(*in), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return rows_in(m->e, m->avail, in, sizeof(*in));
 }
 
 int raft_monitor_read(raft_monitor* m, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_monitor(m, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = m->e;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(out, m->led + 4 * g0, (size_t)n * 64, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_ledger(m, g0, n, "null monitor"), n, out,
+                      [&] { return rows_out(m->e, m->led + 4 * g0, (size_t)n * 64, out); });
 }
 
 int raft_monitor_write(raft_monitor* m, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_monitor(m, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = m->e;
-    const int R = e->p.R;
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t* w = in + k * LEDGER_WORDS;
-        if (((uint32_t)w[0] | (uint32_t)w[1]) & ~(uint32_t)RAFT_MONITOR_ALL)
-            return raft_internal_fail(RAFT_EINVAL, "a ledger's now or ever holds unknown bits");
-        if (w[3] < -1 || w[3] >= R) return raft_internal_fail(RAFT_EINVAL, "a ledger's leader must be in -1..R-1");
-        if ((uint32_t)w[12] >> R) return raft_internal_fail(RAFT_EINVAL, "a ledger's lag_mask holds bits at or above R");
-        if (w[5] < 0 || w[6] < 0 || w[7] < 0 || w[13] < 0 || w[9] < 0)
-            return raft_internal_fail(RAFT_EINVAL,
-                                      "a ledger's outages, down_total, longest, max_lag and stall_mark must be >= 0");
-        if (w[14] || w[15]) return raft_internal_fail(RAFT_EINVAL, "a ledger's reserved words must be 0");
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    HIP_TRY(hipMemcpyAsync(m->led + 4 * g0, in, (size_t)n * 64, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_ledger(m, g0, n, "null monitor"), n, in, [&]() -> int {
+        const int R = m->e->p.R;
+        for (int64_t k = 0; k < n; ++k) {
+            const int32_t* w = in + k * LEDGER_WORDS;
+            if (((uint32_t)w[0] | (uint32_t)w[1]) & ~(uint32_t)RAFT_MONITOR_ALL)
+                return raft_internal_fail(RAFT_EINVAL, "a ledger's now or ever holds unknown bits");
+            if (w[3] < -1 || w[3] >= R) return raft_internal_fail(RAFT_EINVAL, "a ledger's leader must be in -1..R-1");
+            if ((uint32_t)w[12] >> R) return raft_internal_fail(RAFT_EINVAL, "a ledger's lag_mask holds bits at or above R");
+            if (w[5] < 0 || w[6] < 0 || w[7] < 0 || w[13] < 0 || w[9] < 0)
+                return raft_internal_fail(RAFT_EINVAL,
+                                          "a ledger's outages, down_total, longest, max_lag and stall_mark must be >= 0");
+            if (w[14] || w[15]) return raft_internal_fail(RAFT_EINVAL, "a ledger's reserved words must be 0");
+        }
+        m->e->fork_needed = true;
+        return rows_in(m->e, m->led + 4 * g0, in, (size_t)n * 64);
+    });
 }
 
 }  // extern "C"

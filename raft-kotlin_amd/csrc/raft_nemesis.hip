@@ -35,7 +35,7 @@
 
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
@@ -191,7 +191,7 @@ int isolate_dev(raft_engine* e, const int64_t* group, const int32_t* target, con
     Status st;
     if (int rc = st.zero(e, e->cli)) return rc;
     uint32_t* claim = (uint32_t*)(e->cli + Status::BYTES);
-    const unsigned grid = (unsigned)(((int64_t)n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_of(n);
     isolate_clear_kernel<<<grid, BLOCK, 0, e->stream>>>(group, n, e->p.G, claim, st.dev);
     isolate_claim_kernel<<<grid, BLOCK, 0, e->stream>>>(group, target, steps, n, e->p.G, e->p.R, claim);
     isolate_kernel<<<grid, BLOCK, 0, e->stream>>>(e->dp, group, target, steps, flags, claim, (int4*)ticket, n, st.dev);
@@ -226,7 +226,7 @@ int heal(raft_engine* e, int64_t g0, int64_t n, bool host, const uint8_t* mask, 
         HIP_TRY(hipMemcpyAsync(e->aux + Counts::BYTES, mask, (size_t)n, hipMemcpyHostToDevice, e->stream));
         mask = (const uint8_t*)(e->aux + Counts::BYTES);
     }
-    heal_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(e->dp, g0, n, mask, c.dev);
+    heal_kernel<<<grid_of(n), BLOCK, 0, e->stream>>>(e->dp, g0, n, mask, c.dev);
     HIP_TRY(hipGetLastError());
     if (int rc = c.fetch(e)) return rc;
     info->healed = (int64_t)c.w[HL_HEALED];
@@ -238,18 +238,11 @@ int heal(raft_engine* e, int64_t g0, int64_t n, bool host, const uint8_t* mask, 
 int list(raft_engine* e, int64_t g0, int64_t n, raft_isolated* out, int64_t max_events, raft_isolated_info* info,
          bool out_on_host) {
     if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (!info) return raft_internal_fail(RAFT_EINVAL, "null info");
-    *info = raft_isolated_info{};
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (int rc = check_records(out, max_events, out_on_host, 16, "max_events")) return rc;
-    if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;                           // later step launches wait for these reads of the state
-    StreamTotals<IsolatedSource> c{};
-    const int rc = stream_records(e, IsolatedSource{e->dp}, g0, n, out, max_events, out_on_host, c, &info->delivered);
-    info->running = IsolatedSource::total(c.w);
-    info->pending = info->running - info->delivered;
-    return rc;
+    return list_records<IsolatedSource>(e, g0, n, out, max_events, out_on_host, info, &raft_isolated_info::running,
+                                        [&](IsolatedSource& s) {
+                                            s.p = e->dp;
+                                            return RAFT_OK;
+                                        });
 }
 
 }  // namespace

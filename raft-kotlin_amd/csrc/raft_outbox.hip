@@ -57,7 +57,7 @@
 #include <cstddef>
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 #include "raft_ticket.h"
 
 using namespace raft;
@@ -96,18 +96,12 @@ inline int4* half_of(raft_engine* e, int64_t h) {
     return (int4*)(ob_hdr(e) + OB_HDR + (size_t)h * ((e->watch_bytes - seen_bytes(e) - OB_HDR) / 2));
 }
 int ob_load(raft_engine* e, Ob& ob) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(&ob, ob_hdr(e), sizeof(Ob), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (int rc = rows_out(e, ob_hdr(e), sizeof(Ob), &ob)) return rc;
     if (ob.magic != OB_MAGIC || ob.cap < 1 || ob.len < 0 || ob.len > ob.cap || (ob.half & ~(int64_t)1))
         return raft_internal_fail(RAFT_EDEVICE, "the outbox's header is damaged");
     return RAFT_OK;
 }
-int ob_store(raft_engine* e, const Ob& ob) {
-    HIP_TRY(hipMemcpyAsync(ob_hdr(e), &ob, sizeof(Ob), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
-}
+int ob_store(raft_engine* e, const Ob& ob) { return rows_in(e, ob_hdr(e), &ob, sizeof(Ob)); }
 
 __device__ __forceinline__ int64_t i64_of(int32_t lo, int32_t hi) {
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
@@ -291,7 +285,7 @@ int submit(raft_engine* e, const int64_t* group, const uint32_t* cmd, const int6
     if (int rc = raft_internal_grow_dev(e, &e->apl, &e->apl_bytes, OBS_HEAD)) return rc;
     Flag f;
     if (int rc = f.zero(e, e->apl + OBS_FLAG)) return rc;
-    outbox_submit_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
+    outbox_submit_kernel<<<grid_of(n), BLOCK, 0, e->stream>>>(
         half_of(e, ob.half), ob.len, group, cmd, tag, n, (int64_t)e->t, e->p.G, f.dev);
     HIP_TRY(hipGetLastError());
     if (int rc = f.fetch(e)) return rc;
@@ -350,12 +344,12 @@ int pump(raft_engine* e, raft_outbox_done* done, int64_t max_done, int64_t* n_do
         raft_ticket* rtk = (raft_ticket*)(rb + g_b + 2 * u_b);
         if (int rc = sc.run(e)) return rc;
         int4* q_out = half_of(e, ob.half ^ 1);
-        outbox_split_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
+        outbox_split_kernel<<<grid_of(n), BLOCK, 0, e->stream>>>(
             q, q_out, verdict, sc.off, n, max_done, now, (int4*)rec.dev, rg, rc_, rpos, hist.dev);
         HIP_TRY(hipGetLastError());
         if (n_retry > 0) {
             if (int rc = raft_internal_propose_enqueue(e, rg, rc_, rtk, (int)n_retry)) return rc;
-            outbox_scatter_kernel<<<(unsigned)((n_retry + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
+            outbox_scatter_kernel<<<grid_of(n_retry), BLOCK, 0, e->stream>>>(
                 q_out, rpos, (const int4*)rtk, n_retry, tot.dev);
             HIP_TRY(hipGetLastError());
         }
@@ -460,9 +454,7 @@ int raft_engine_outbox_read(raft_engine* e, raft_outbox_entry* out, int64_t room
     if (!out && room == 0) return RAFT_OK;           // a peek: the queue's length
     if (!out || room < ob.len) return raft_internal_fail(RAFT_EINVAL, "the buffer has no room for the queue");
     if (ob.len == 0) return RAFT_OK;
-    HIP_TRY(hipMemcpyAsync(out, half_of(e, ob.half), (size_t)ob.len * REC, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return rows_out(e, half_of(e, ob.half), (size_t)ob.len * REC, out);
 }
 
 int raft_engine_outbox_write(raft_engine* e, const raft_outbox_entry* in, int64_t n) {
@@ -483,10 +475,8 @@ int raft_engine_outbox_write(raft_engine* e, const raft_outbox_entry* in, int64_
             return raft_internal_fail(RAFT_EINVAL, "a record's ticket (status, replica, index), tries or pad is outside "
                                                    "what a pump accepts: nothing was stored");
     }
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(half_of(e, ob.half), in, (size_t)n * REC, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
+    if (n > 0)
+        if (int rc = rows_in(e, half_of(e, ob.half), in, (size_t)n * REC)) return rc;
     ob.len = n;
     return ob_store(e, ob);
 }

@@ -32,7 +32,7 @@
 
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
@@ -344,17 +344,14 @@ int raft_engine_sm_apply(raft_engine* e, int64_t g0, int64_t n, int32_t replica,
     return RAFT_OK;
 }
 
+// replicas are indexed g * R + r: a range of groups is one contiguous run of heads and one of registers; either
+// pointer may be null (that region is skipped), so the shared head's null-buffer refusal does not apply
 int raft_engine_sm_read(raft_engine* e, int64_t g0, int64_t n, raft_sm_head* heads, uint32_t* regs) {
     if (int rc = check_sm(e)) return rc;
     if (int rc = check_groups(e, g0, n)) return rc;
     if (n == 0) return RAFT_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    // replicas are indexed g * R + r: the range is one contiguous run of heads and of registers
     const size_t r0 = (size_t)g0 * e->p.R, rn = (size_t)n * e->p.R, S = (size_t)e->sm_slots;
-    if (heads) HIP_TRY(hipMemcpyAsync(heads, sm_heads_of(e) + r0, rn * 16, hipMemcpyDeviceToHost, e->stream));
-    if (regs) HIP_TRY(hipMemcpyAsync(regs, sm_regs_of(e) + r0 * S, rn * S * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return rows_out(e, {{sm_heads_of(e) + r0, heads, rn * 16}, {sm_regs_of(e) + r0 * S, regs, rn * S * 4}});
 }
 
 int raft_engine_sm_write(raft_engine* e, int64_t g0, int64_t n, const raft_sm_head* heads, const uint32_t* regs) {
@@ -368,11 +365,7 @@ int raft_engine_sm_write(raft_engine* e, int64_t g0, int64_t n, const raft_sm_he
                 return raft_internal_fail(RAFT_EINVAL, "applied must be in 0..log_cap");
             if (heads[k].lost < 0) return raft_internal_fail(RAFT_EINVAL, "lost must be >= 0");
         }
-    HIP_TRY(hipSetDevice(e->device));
-    if (heads) HIP_TRY(hipMemcpyAsync(sm_heads_of(e) + r0, heads, rn * 16, hipMemcpyHostToDevice, e->stream));
-    if (regs) HIP_TRY(hipMemcpyAsync(sm_regs_of(e) + r0 * S, regs, rn * S * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return rows_in(e, {{sm_heads_of(e) + r0, heads, rn * 16}, {sm_regs_of(e) + r0 * S, regs, rn * S * 4}});
 }
 
 int raft_engine_sm_get(raft_engine* e, const int64_t* group, const int32_t* replica, const uint32_t* key,
@@ -389,7 +382,7 @@ int raft_engine_sm_get(raft_engine* e, const int64_t* group, const int32_t* repl
     if (int rc = raft_internal_grow_dev(e, &e->cli, &e->cli_bytes, GW_BYTES)) return rc;
     GetStatus st;
     if (int rc = st.zero(e, e->cli)) return rc;
-    sm_get_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(
+    sm_get_kernel<<<grid_of(n), BLOCK, 0, e->stream>>>(
         e->dp, e->sm_slots, sm_heads_of(e), sm_regs_of(e), (const int64_t*)(e->cio + s.off[0]),
         (const int32_t*)(e->cio + s.off[1]), (const uint32_t*)(e->cio + s.off[2]), (int4*)(e->cio + s.out_off), (int)n,
         st.dev);
@@ -414,7 +407,7 @@ int raft_engine_sm_check(raft_engine* e, int64_t g0, int64_t n, uint8_t* flags, 
     uint8_t* fl = flags ? (uint8_t*)e->aux + 8 : nullptr;
     unsigned long long h = 0;
     HIP_TRY(hipMemsetAsync(cnt, 0, 8, e->stream));
-    sm_check_kernel<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(e->dp, sm_heads_of(e), g0, n, fl, cnt);
+    sm_check_kernel<<<grid_of(n), BLOCK, 0, e->stream>>>(e->dp, sm_heads_of(e), g0, n, fl, cnt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, e->stream));
     if (flags) HIP_TRY(hipMemcpyAsync(flags, fl, (size_t)n, hipMemcpyDeviceToHost, e->stream));

@@ -17,6 +17,9 @@
 
 namespace {
 
+// workgroups of BLOCK threads for n threads
+inline unsigned grid_of(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
 // ---- the striped tally (DevWords, raft_engine_impl.h): the line of stripe
 // (index mod HDR_STRIPES), lines `stride` words apart; index is the wave's
 // number in the grid unless the caller counts its waves another way
@@ -195,7 +198,7 @@ int stream_records(raft_engine* e, const S& src, int64_t g0, int64_t n, void* ou
     ScanScratch<uint32_t> sc;
     if (int rc = sc.init(e, &e->aux, &e->aux_bytes, StreamTotals<S>::BYTES, (size_t)((n + 63) / 64))) return rc;
     if (int rc = t.zero(e, sc.head)) return rc;
-    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    const unsigned grid = grid_of(n);
     stream_flag_kernel<S><<<grid, BLOCK, 0, e->stream>>>(src, g0, n, sc.cnt, t.dev);
     HIP_TRY(hipGetLastError());
     if (int rc = t.fetch(e)) return rc;

@@ -45,14 +45,11 @@
 #include <algorithm>
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
-struct raft_wal {
-    raft_engine* e;
-    char* mem;                  // one allocation: the cursors [G * R] of 24 bytes
-    size_t bytes;
+struct raft_wal : raft_ledger {   // mem: the cursors [G * R] of 24 bytes
     uint2* cur;
 };
 
@@ -277,8 +274,7 @@ __global__ __launch_bounds__(BLOCK) void wal_expand_kernel(DevParams p, uint2* _
 
 template <int R> struct CountW {
     static void run(raft_engine* e, const uint2* cur, const Sel& s, uint32_t* cnt, uint8_t* flg, unsigned long long* hdr) {
-        const unsigned grid = (unsigned)((s.N + 1 + BLOCK - 1) / BLOCK);
-        wal_count_kernel<R><<<grid, BLOCK, 0, e->stream>>>(e->dp, cur, s, cnt, flg, hdr);
+        wal_count_kernel<R><<<grid_of(s.N + 1), BLOCK, 0, e->stream>>>(e->dp, cur, s, cnt, flg, hdr);
     }
 };
 template <int R> struct ExpandW {
@@ -289,11 +285,6 @@ template <int R> struct ExpandW {
         wal_expand_kernel<R><<<grid, BLOCK, 0, e->stream>>>(e->dp, cur, s, cnt, flg, off, out, max_records, hdr);
     }
 };
-
-int check_wal(raft_wal* w, int64_t g0, int64_t n) {
-    if (!w || !w->e) return raft_internal_fail(RAFT_EINVAL, "null wal");
-    return check_groups(w->e, g0, n);
-}
 
 int poll(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_wal_record* out, int64_t max_records,
          raft_wal_info* info, bool out_on_host) {
@@ -349,51 +340,25 @@ int poll(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_wal_record* o
 extern "C" {
 
 int raft_wal_create(raft_engine* e, raft_wal** out) {
-    if (!e) return raft_internal_fail(RAFT_EINVAL, "null engine");
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null out");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(e->device));
-    raft_wal* w = new raft_wal{};
-    w->e = e;
-    w->bytes = al256((size_t)e->dp.GR * sizeof(raft_wal_cursor));
-    if (hipMalloc((void**)&w->mem, w->bytes) != hipSuccess) {
-        delete w;
-        return raft_internal_fail(RAFT_ENOMEM, "the wal's cursors: hipMalloc failed");
-    }
-    w->cur = (uint2*)w->mem;
-    if (int rc = raft_wal_reset(w)) {
-        (void)hipFree(w->mem);
-        delete w;
-        return rc;
-    }
-    *out = w;
-    return RAFT_OK;
+    if (int rc = create_args(e, out)) return rc;
+    return ledger_create(e, out, al256((size_t)e->dp.GR * sizeof(raft_wal_cursor)), "the wal's cursors", [](raft_wal* w) {
+        w->cur = (uint2*)w->mem;
+        return raft_wal_reset(w);
+    });
 }
 
-int raft_wal_destroy(raft_wal* w) {
-    if (!w) return RAFT_OK;
-    if (w->e) {
-        (void)hipSetDevice(w->e->device);
-        (void)hipStreamSynchronize(w->e->stream);
-    }
-    (void)hipFree(w->mem);
-    delete w;
-    return RAFT_OK;
-}
+int raft_wal_destroy(raft_wal* w) { return ledger_destroy(w); }
 
 int raft_wal_reset(raft_wal* w) {
-    if (int rc = check_wal(w, 0, 0)) return rc;
-    raft_engine* e = w->e;
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    const unsigned grid = (unsigned)((e->dp.GR + BLOCK - 1) / BLOCK);
-    wal_fill_kernel<<<grid, BLOCK, 0, e->stream>>>(w->cur, e->dp.GR);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return ledger_reset(w, "null wal", [&](raft_engine* e) -> int {
+        e->fork_needed = true;
+        wal_fill_kernel<<<grid_of(e->dp.GR), BLOCK, 0, e->stream>>>(w->cur, e->dp.GR);
+        HIP_TRY(hipGetLastError());
+        return RAFT_OK;
+    });
 }
 
-int64_t raft_wal_device_bytes(raft_wal* w) { return w ? (int64_t)w->bytes : 0; }
+int64_t raft_wal_device_bytes(raft_wal* w) { return ledger_bytes(w); }
 
 int raft_wal_poll(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_wal_record* out_host, int64_t max_records,
                   raft_wal_info* info) {
@@ -405,40 +370,30 @@ int raft_wal_poll_dev(raft_wal* w, int64_t g0, int64_t n, int32_t replica, raft_
     return poll(w, g0, n, replica, out_dev, max_records, info, false);
 }
 
+// replicas are indexed g * R + r: a range of groups is one contiguous run of cursors
 int raft_wal_read(raft_wal* w, int64_t g0, int64_t n, raft_wal_cursor* cursors) {
-    if (int rc = check_wal(w, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!cursors) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = w->e;
-    HIP_TRY(hipSetDevice(e->device));
-    // replicas are indexed g * R + r: the range is one contiguous run
-    HIP_TRY(hipMemcpyAsync(cursors, w->cur + 3 * g0 * e->p.R, (size_t)n * e->p.R * sizeof(raft_wal_cursor),
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_ledger(w, g0, n, "null wal"), n, cursors, [&] {
+        const int64_t R = w->e->p.R;
+        return rows_out(w->e, w->cur + 3 * g0 * R, (size_t)(n * R) * sizeof(raft_wal_cursor), cursors);
+    });
 }
 
 int raft_wal_write(raft_wal* w, int64_t g0, int64_t n, const raft_wal_cursor* cursors) {
-    if (int rc = check_wal(w, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!cursors) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    raft_engine* e = w->e;
-    for (int64_t k = 0; k < n * e->p.R; ++k) {       // a poll reads log slots [stable - 1, lastIndex): keep it inside the row
-        const raft_wal_cursor& c = cursors[k];
-        const char* why = c.stable < 0 || c.stable > e->p.log_cap ? "a cursor's stable must be in 0..log_cap"
-                          : c.floor < 0 || c.floor > c.stable   ? "a cursor's floor must be in 0..stable"
-                          : c.vote < -1 || c.vote > e->p.R      ? "a cursor's vote must be in -1..R"
-                          : c.term < 0                          ? "a cursor's term must be >= 0"
-                          : c.pad                               ? "a cursor's pad must be 0"
-                                                                : nullptr;
-        if (why) return raft_internal_fail(RAFT_EINVAL, why);
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    e->fork_needed = true;
-    HIP_TRY(hipMemcpyAsync(w->cur + 3 * g0 * e->p.R, cursors, (size_t)n * e->p.R * sizeof(raft_wal_cursor),
-                           hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_ledger(w, g0, n, "null wal"), n, cursors, [&]() -> int {
+        raft_engine* e = w->e;
+        for (int64_t k = 0; k < n * e->p.R; ++k) {   // a poll reads log slots [stable - 1, lastIndex): keep it inside the row
+            const raft_wal_cursor& c = cursors[k];
+            const char* why = c.stable < 0 || c.stable > e->p.log_cap ? "a cursor's stable must be in 0..log_cap"
+                              : c.floor < 0 || c.floor > c.stable   ? "a cursor's floor must be in 0..stable"
+                              : c.vote < -1 || c.vote > e->p.R      ? "a cursor's vote must be in -1..R"
+                              : c.term < 0                          ? "a cursor's term must be >= 0"
+                              : c.pad                               ? "a cursor's pad must be 0"
+                                                                    : nullptr;
+            if (why) return raft_internal_fail(RAFT_EINVAL, why);
+        }
+        e->fork_needed = true;
+        return rows_in(e, w->cur + 3 * g0 * e->p.R, cursors, (size_t)n * e->p.R * sizeof(raft_wal_cursor));
+    });
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 
 #include <string>
 
-#include "raft_stream.h"
+#include "raft_ledger.h"
 
 using namespace raft;
 
@@ -116,8 +116,7 @@ int raft_internal_outbox_reset(raft_engine* e);
 int raft_internal_watch_reset(raft_engine* e) {
     if (!e->watch) return RAFT_OK;
     if (int rc = raft_internal_outbox_reset(e)) return rc;
-    const unsigned grid = (unsigned)((e->p.G + BLOCK - 1) / BLOCK);
-    watch_fill_kernel<<<grid, BLOCK, 0, e->stream>>>(e->watch, e->p.G);
+    watch_fill_kernel<<<grid_of(e->p.G), BLOCK, 0, e->stream>>>(e->watch, e->p.G);
     HIP_TRY(hipGetLastError());
     return RAFT_OK;
 }
@@ -134,31 +133,26 @@ int raft_engine_poll_leaders_dev(raft_engine* e, int64_t g0, int64_t n, raft_lea
     return poll(e, g0, n, out_dev, max_events, info, false);
 }
 
+// the pairs are allocated at the first call that needs them: before the copy, on the engine's device
 int raft_engine_read_watch(raft_engine* e, int64_t g0, int64_t n, int32_t* out) {
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!out) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = ensure_watch(e)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->watch + g0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_groups(e, g0, n), n, out, [&]() -> int {
+        HIP_TRY(hipSetDevice(e->device));
+        if (int rc = ensure_watch(e)) return rc;
+        return rows_out(e, e->watch + g0, (size_t)n * sizeof(int2), out);
+    });
 }
 
 int raft_engine_write_watch(raft_engine* e, int64_t g0, int64_t n, const int32_t* in) {
-    if (int rc = check_groups(e, g0, n)) return rc;
-    if (n == 0) return RAFT_OK;
-    if (!in) return raft_internal_fail(RAFT_EINVAL, "null buffer");
-    for (int64_t k = 0; k < n; ++k) {
-        const int32_t leader = in[2 * k], term = in[2 * k + 1];
-        if (leader < -1 || leader >= e->p.R || term < 0 || (leader < 0 && term != 0))
-            return raft_internal_fail(RAFT_EINVAL, "a watch pair is (-1, 0) or (leader in 0..R-1, term >= 0)");
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = ensure_watch(e)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->watch + g0, in, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return RAFT_OK;
+    return table_call(check_groups(e, g0, n), n, in, [&]() -> int {
+        for (int64_t k = 0; k < n; ++k) {
+            const int32_t leader = in[2 * k], term = in[2 * k + 1];
+            if (leader < -1 || leader >= e->p.R || term < 0 || (leader < 0 && term != 0))
+                return raft_internal_fail(RAFT_EINVAL, "a watch pair is (-1, 0) or (leader in 0..R-1, term >= 0)");
+        }
+        HIP_TRY(hipSetDevice(e->device));
+        if (int rc = ensure_watch(e)) return rc;
+        return rows_in(e, e->watch + g0, in, (size_t)n * sizeof(int2));
+    });
 }
 
 }  // extern "C"
